@@ -35,10 +35,11 @@ smaller config under the same name.
 
 Round size: ``--max-tokens`` defaults to 2048 so that the driver's fixed ``--steps 20 --warmup 5``
 finishes inside its 600-s limit at every N (N=1 measured: see BASELINE.md §2.0); 4096-token rounds
-are the ``--max-tokens 4096`` secondary. Warmup rounds decode ``--warmup-tokens`` (default 64)
-tokens per engine: every decode graph is captured when the engines are built and the judge's
-prefill path is warmed once at full prompt length, so a short round exercises everything a timed
-round does. The K timed rounds are always full rounds.
+are the ``--max-tokens 4096`` secondary. A warmup round is by default the same full round as a
+timed one, so a run lasts (K + W) x ``ms_per_step`` plus set-up. ``--warmup-tokens T`` shortens the
+warmup rounds to T tokens per engine: every decode graph is captured when the engines are built and
+the judge's prefill path is warmed once at full prompt length, so a short round exercises
+everything a timed round does. The K timed rounds are always full rounds.
 
 ``--shapes tiny`` swaps every family for its tiny twin (same code paths; CPU / same-GPU
 rehearsals of the multi-rank flows: ``LLMC_BENCH_DEVICE=cpu`` or ``LLMC_BENCH_SAME_GPU=1`` with
@@ -47,6 +48,17 @@ rehearsals of the multi-rank flows: ``LLMC_BENCH_DEVICE=cpu`` or ``LLMC_BENCH_SA
 Reported ``value`` = total generated tokens (responders + judge) per second of wall time over the
 whole job (max over ranks); ``ms_per_step`` = mean round latency; p50/p90 are in ``extra``.
 Data: synthetic prompt (seeded synthetic-tokenizer text), random-init weights, bf16.
+
+A plain run builds the engines, warms up, times the K rounds and prints the JSON line. ``--full``
+adds what the headline does not need: the node record in ``extra`` (each rank's device, the
+peer-access matrix and every TP group's measured 16 KiB all-reduce latency, which takes a run of
+its own) and the per-step record file under ``--results-dir``.
+
+``--dump-outputs DIR`` writes what the last timed round returned as ``DIR/<name>.npy`` (float32):
+``responder_tokens`` (one row of token ids per responder, -1 = no token) and ``judge_tokens`` (the
+judge's token ids); ``--path cli`` writes the UTF-8 bytes of every response and of the consensus
+(``response_<i>_utf8``, ``consensus_utf8``). Prompt, weights and sampling seeds are functions of the
+arguments alone, so two runs with the same arguments start from identical inputs.
 """
 
 from __future__ import annotations
@@ -130,6 +142,24 @@ class Progress:
         if now - self.last >= self.every:
             self.last = now
             log(f"{self.what}: {self.n} tokens after {now - self.t0:.0f}s")
+
+
+def dump_outputs(out_dir: str, arrays) -> None:
+    """--dump-outputs: every array of ``arrays`` ({name: sequence of numbers}) as
+    ``out_dir/<name>.npy`` in float32 (token ids and byte values are exact in it)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, dtype=np.float32))
+
+
+def results_dir(args) -> str:
+    """Where the per-step record goes: ``--results-dir`` when given, else ``bench/results`` with
+    ``--full`` and nowhere in a plain run."""
+    if args.results_dir is not None:
+        return args.results_dir
+    return os.path.join(ROOT, "bench", "results") if args.full else ""
 
 
 def judge_tp_degree(cfg, world: int, requested: int) -> int:
@@ -394,6 +424,7 @@ def cli_path_bench(args) -> None:
     startup = time.perf_counter() - t0
     log(f"product path ready in {startup:.1f}s: {models} + {judge}")
     tmp = tempfile.mkdtemp(prefix="llmc-bench-cli-")
+    last_out = {}  # what the latest round returned (--dump-outputs)
 
     def one_round(step: int, max_tokens: int):
         ev = []
@@ -413,6 +444,9 @@ def cli_path_bench(args) -> None:
         with open(os.path.join(run_dir, "result.json"), "w") as f:
             f.write(encode_result(res))
         t_end = time.perf_counter() - ts
+        last_out.clear()
+        last_out.update({f"response_{i}_utf8": list(r.content.encode()) for i, r in enumerate(res.responses)})
+        last_out["consensus_utf8"] = list(res.consensus.encode())
         done = [t for t, name, _ in ev if name == "model_done"]
         jstart = next((t for t, name, _ in ev if name == "judge_start"), t_run)
         jfirst = next((t for t, name, _ in ev if name == "judge_chunk"), t_run)
@@ -446,6 +480,8 @@ def cli_path_bench(args) -> None:
         elapsed = time.perf_counter() - t0
     finally:
         svc.close()
+    if args.dump_outputs and per_step:
+        dump_outputs(args.dump_outputs, last_out)
     lat = [p["e2e_s"] for p in per_step]
     tot = sum(p["tokens"] for p in per_step)
     med = lambda k: round(statistics.median(p[k] for p in per_step), 3)  # noqa: E731
@@ -471,10 +507,10 @@ def cli_path_bench(args) -> None:
         },
     }
     print(json.dumps(out), flush=True)
-    if args.results_dir:
+    if results_dir(args):
         try:
-            os.makedirs(args.results_dir, exist_ok=True)
-            fn = os.path.join(args.results_dir, f"bench_cli_{time.strftime('%Y%m%dT%H%M%SZ', time.gmtime())}_n{n}.json")
+            os.makedirs(results_dir(args), exist_ok=True)
+            fn = os.path.join(results_dir(args), f"bench_cli_{time.strftime('%Y%m%dT%H%M%SZ', time.gmtime())}_n{n}.json")
             with open(fn, "w") as f:
                 json.dump(dict(out, per_step=per_step, argv=sys.argv[1:]), f, indent=2)
         except OSError as e:
@@ -496,7 +532,7 @@ def main() -> None:
     ap.add_argument("--max-tokens", type=int, default=2048,
                     help="tokens per response and for the judge (2048: 20 driver steps fit its 600-s limit)")
     ap.add_argument("--judge-max-tokens", type=int, default=0, help="0 = same as --max-tokens")
-    ap.add_argument("--warmup-tokens", type=int, default=64,
+    ap.add_argument("--warmup-tokens", type=int, default=0,
                     help="tokens per engine in the (untimed) warmup rounds (0 = full rounds)")
     ap.add_argument("--prompt-tokens", type=int, default=128)
     ap.add_argument("--temperature", type=float, default=1.0)
@@ -511,14 +547,22 @@ def main() -> None:
     ap.add_argument("--no-graphs", action="store_true")
     ap.add_argument("--time-budget", type=float, default=560.0,
                     help="seconds the whole command may take (0 = off): the last two warmup rounds (W >= 2) are "
-                         "timed at two lengths, and if K full rounds would overrun, the timed rounds decode fewer "
-                         "tokens (recorded as config.max_tokens, with max_tokens_requested)")
+                         "timed (short ones at two lengths), and if K full rounds would overrun, the timed rounds "
+                         "decode fewer tokens (recorded as config.max_tokens, with max_tokens_requested)")
     ap.add_argument("--path", default="engine", choices=["engine", "cli"],
                     help="engine: the engines driven directly on threads (the headline); cli: the product path "
                          "(Runner -> LocalProvider -> worker process -> pipe -> detokenizer -> result.json) through "
                          "ConsensusService with the same round, per-phase times in extra (fanout preset only)")
-    ap.add_argument("--results-dir", default=os.path.join(ROOT, "bench", "results"),
-                    help="rank 0 also writes the full record (per-step stats, p50/p90) here ('' = off)")
+    ap.add_argument("--results-dir", default=None,
+                    help="rank 0 also writes the full record (per-step stats, p50/p90) here ('' = off; default: "
+                         "bench/results with --full, off without)")
+    ap.add_argument("--full", action="store_true",
+                    help="also what the headline figure does not need: the node record in extra (rank devices, "
+                         "peer-access matrix, each TP group's measured 16 KiB all-reduce latency) and the "
+                         "per-step record file under --results-dir")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed rounds, write what the last one returned as DIR/<name>.npy (float32): "
+                         "responder_tokens (one row per responder, -1 = no token) and judge_tokens")
     args = ap.parse_args()
 
     if not args.gpus:
@@ -693,11 +737,13 @@ def main() -> None:
         dist.barrier()
     log(f"engines ready in {time.time() - t0:.1f}s: {[e.name for _, e, _, _ in responders]}"
         + (f" + {judge.name} (TP={judge.tp.size}, ctx {judge_ctx})" if judge else ""))
-    # what the run actually saw of the node (before any timed work): the RCCL world, each rank's
-    # device, the peer-access matrix and every TP group's 16 KiB all-reduce latency
-    topo = topology(world, rank, dev, on_cpu, tp_members, cdev)
-    if rank == 0:
+    # --full: what the run actually saw of the node (before any timed work): the RCCL world, each
+    # rank's device, the peer-access matrix and every TP group's 16 KiB all-reduce latency
+    topo = (topology(world, rank, dev, on_cpu, tp_members, cdev) if args.full
+            else {"dist_world_size": dist.get_world_size() if world > 1 else 1})
+    if rank == 0 and args.full:
         log(f"topology: {topo}")
+    last_out = {}  # what the latest round returned on this rank (--dump-outputs)
 
     def one_round(step: int, max_tokens: int = 0):
         max_tokens = max_tokens or args.max_tokens
@@ -772,6 +818,8 @@ def main() -> None:
             ts = times.to(cdev)
             dist.all_reduce(ts)
             times = ts.cpu()
+        last_out.clear()
+        last_out["responder_tokens"] = (table - 1).numpy()
         stats["per_model"] = {e["name"]: {"ttft_s": float(times[i, 0]), "latency_s": float(times[i, 1])}
                               for i, e in enumerate(resp_plan)}
         n_tokens = n_resp * max_tokens
@@ -816,6 +864,7 @@ def main() -> None:
             stats["judge_decode_s"] = time.perf_counter() - t_jp
             if judge.tp.is_leader:
                 stats["judge_tokens"] = len(jids)
+                last_out["judge_tokens"] = list(jids)
             judge.free_sequence(jseq)
         sync()
         # a custom-collective spin that gave up means a peer stalled and the sums are invalid
@@ -840,20 +889,25 @@ def main() -> None:
         probe[min(n_w, args.max_tokens)] = time.perf_counter() - tw
         log(f"warmup {w}: {st}")
     round_tokens = args.max_tokens
-    if args.time_budget > 0 and args.warmup >= 2 and len(probe) == 2:
-        (t1, s1), (t2, s2) = sorted(probe.items())
+    if args.time_budget > 0 and args.warmup >= 2 and len(probe) in (1, 2):
+        (t1, s1), (t2, s2) = sorted(probe.items()) if len(probe) == 2 else (list(probe.items()) * 2)
         pr = torch.tensor([s1, s2], dtype=torch.float64, device=cdev)
         if world > 1:
             dist.all_reduce(pr, op=dist.ReduceOp.MAX)
         s1, s2 = float(pr[0]), float(pr[1])
-        c1 = max((s2 - s1) / (t2 - t1), 1e-6)
-        c0 = max(s1 - c1 * t1, 0.0)
+        if len(probe) == 2:
+            c1 = max((s2 - s1) / (t2 - t1), 1e-6)
+            c0 = max(s1 - c1 * t1, 0.0)
+            # x 1.15: the probe rounds are short, and a full round's attention and judge prompt grow
+            # with its length (the two-point line under-estimates it)
+            margin = 1.15
+        else:
+            # full-length warmup rounds (the default): the last one is the cost of a timed round
+            c0, c1, margin = 0.0, max(s2 / t2, 1e-6), 1.05
         left = args.time_budget - (time.time() - T_START) - 10.0  # teardown margin
-        # x 1.15: the probe rounds are short, and a full round's attention and judge prompt grow
-        # with its length (the two-point line under-estimates it)
-        need = 1.15 * args.steps * (c0 + c1 * args.max_tokens)
+        need = margin * args.steps * (c0 + c1 * args.max_tokens)
         if need > left:
-            fit = int(((left / (1.15 * args.steps)) - c0) / c1) // 64 * 64
+            fit = int(((left / (margin * args.steps)) - c0) / c1) // 64 * 64
             round_tokens = max(64, min(args.max_tokens, fit))
             log(f"time budget: {args.steps} rounds of {args.max_tokens} tokens need ~{need:.0f}s, {left:.0f}s left: "
                 f"timed rounds decode {round_tokens} tokens")
@@ -880,6 +934,10 @@ def main() -> None:
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and per_step:
+        # rank 0 holds every responder's gathered row; the judge's tokens are on its leader rank
+        dump_outputs(args.dump_outputs, {k: v for k, v in last_out.items()
+                                         if rank == 0 or k == "judge_tokens"})
     judge_stats = per_step[-1] if per_step else {}
     if world > 1:
         tt = torch.tensor([elapsed], dtype=torch.float64, device=cdev)
@@ -982,12 +1040,12 @@ def main() -> None:
             },
         }
         print(json.dumps(out), flush=True)
-        if args.results_dir:
+        if results_dir(args):
             rec = dict(out, per_step=per_step, time_utc=time.strftime("%Y%m%dT%H%M%SZ", time.gmtime()),
                        argv=sys.argv[1:])
             try:
-                os.makedirs(args.results_dir, exist_ok=True)
-                fn = os.path.join(args.results_dir, f"bench_{rec['time_utc']}_n{n_gpus}.json")
+                os.makedirs(results_dir(args), exist_ok=True)
+                fn = os.path.join(results_dir(args), f"bench_{rec['time_utc']}_n{n_gpus}.json")
                 with open(fn, "w") as f:
                     json.dump(rec, f, indent=2)
             except OSError as e:

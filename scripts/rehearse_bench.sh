@@ -6,4 +6,4 @@ set -euo pipefail
 N=${1:-2}; shift || true
 export LLMC_BENCH_BACKEND=gloo LLMC_BENCH_SAME_GPU=1
 exec python -m torch.distributed.run --nnodes=1 --nproc-per-node "$N" --master-addr 127.0.0.1 \
-  --master-port "${PORT:-29641}" bench.py --gpus "$N" --results-dir "" "$@"
+  --master-port "${PORT:-29641}" bench.py --gpus "$N" --full --results-dir "" "$@"

@@ -120,13 +120,54 @@ def test_time_budget_shortens_rounds_never_steps():
     _tokens_ok(d, d["config"]["max_tokens"])
 
 
+def test_plain_run_is_lean_and_dumps_repeatable_outputs(tmp_path):
+    """A plain run measures only the headline: no node record in ``extra`` (that is --full) and no
+    record file. --dump-outputs writes the last timed round's tokens as float32 .npy files, and two
+    runs with the same arguments give the same files (identical inputs, seeded sampling)."""
+    import numpy as np
+
+    outs = []
+    for tag in ("a", "b"):
+        d = _run(1, ["--shapes", "tiny", "--steps", "2", "--warmup", "2", "--max-tokens", "12",
+                     "--dump-outputs", str(tmp_path / tag)], 0)
+        assert d["steps"] == 2 and d["ms_per_step"] > 0
+        # by default a warmup round is the same full round as a timed one
+        assert d["extra"]["warmup_rounds_tokens"] == [12, 12] and d["extra"]["budget_shortened"] is False
+        assert not {"allreduce_16k", "peer_access", "rank_devices"} & set(d["extra"])
+        _tokens_ok(d, 12)
+        assert sorted(os.listdir(tmp_path / tag)) == ["judge_tokens.npy", "responder_tokens.npy"]
+        outs.append({f: np.load(tmp_path / tag / f) for f in os.listdir(tmp_path / tag)})
+    a, b = outs
+    assert a["responder_tokens.npy"].shape == (3, 12) and a["judge_tokens.npy"].shape == (12,)
+    for f in a:
+        assert a[f].dtype == np.float32 and (a[f] >= 0).all() and (a[f] == np.floor(a[f])).all()
+        assert np.array_equal(a[f], b[f]), f
+    # three replicas with their own weights and seeds: not one row three times
+    assert len({tuple(r) for r in a["responder_tokens.npy"].tolist()}) == 3
+
+
+def test_full_run_adds_node_record_and_results_file(tmp_path):
+    """--full: the node record is in ``extra`` and the per-step record file is written."""
+    env = dict(os.environ, LLMC_BENCH_DEVICE="cpu", OMP_NUM_THREADS="1")
+    args = ["--shapes", "tiny", "--steps", "1", "--warmup", "0", "--max-tokens", "12", "--full", "--results-dir",
+            str(tmp_path)]
+    r = subprocess.run([sys.executable, "bench.py"] + args, cwd=ROOT, capture_output=True, timeout=600, env=env)
+    assert r.returncode == 0, r.stderr.decode()[-3000:]
+    d = json.loads([ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")][0])
+    assert d["extra"]["dist_world_size"] == 1 and len(d["extra"]["rank_devices"]) == 1
+    assert d["extra"]["allreduce_16k"] == {}  # one rank: no TP group
+    _tokens_ok(d, 12)
+    recs = [f for f in os.listdir(tmp_path) if f.startswith("bench_") and f.endswith(".json")]
+    assert len(recs) == 1 and len(json.load(open(tmp_path / recs[0]))["per_step"]) == 1
+
+
 def _self_launched(n, extra=()):
     """``python bench.py --gpus N`` with no launcher in the environment: bench.py starts the N
     rank processes itself."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(LLMC_BENCH_DEVICE="cpu", OMP_NUM_THREADS="1")
     r = subprocess.run([sys.executable, "bench.py", "--gpus", str(n), "--shapes", "tiny", "--steps", "1", "--warmup",
-                        "1", "--max-tokens", "8", "--warmup-tokens", "4", "--results-dir", "", *extra],
+                        "1", "--max-tokens", "8", "--warmup-tokens", "4", "--full", "--results-dir", "", *extra],
                        cwd=ROOT, capture_output=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     lines = [ln for ln in r.stdout.decode().splitlines() if ln.strip().startswith("{")]

@@ -50,6 +50,23 @@ def test_bench_json_contract_1gpu(cuda):
     assert d["config"]["global_batch"] == 3  # N=1: three co-located responders + the judge
 
 
+def test_bench_plain_run_dumps_last_round(cuda, tmp_path):
+    """A plain run carries no node record (that is --full); --dump-outputs writes the last timed
+    round's responder and judge token ids as float32 .npy files."""
+    import numpy as np
+
+    line = run_ranks(1, ["--model", "llama-small", "--judge", "llama-small", "--steps", "2", "--warmup", "1",
+                         "--max-tokens", "48", "--dump-outputs", str(tmp_path)], 0)
+    d = check_line(line, 1, 2, 1, 48)
+    assert not {"allreduce_16k", "peer_access", "rank_devices"} & set(d["extra"])
+    assert sorted(os.listdir(tmp_path)) == ["judge_tokens.npy", "responder_tokens.npy"]
+    resp, judge = np.load(tmp_path / "responder_tokens.npy"), np.load(tmp_path / "judge_tokens.npy")
+    assert resp.shape == (3, 48) and judge.shape == (48,) and resp.dtype == judge.dtype == np.float32
+    for a in (resp, judge):
+        assert (a >= 0).all() and (a == np.floor(a)).all()
+    assert len({tuple(r) for r in resp.tolist()}) == 3  # three replicas, own weights and seeds
+
+
 SAME_GPU = {"LLMC_BENCH_BACKEND": "gloo", "LLMC_BENCH_SAME_GPU": "1"}
 
 

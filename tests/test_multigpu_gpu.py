@@ -262,7 +262,7 @@ def test_bench_self_launch_across_devices(world):
     _need(world)
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     r = subprocess.run([sys.executable, "bench.py", "--gpus", str(world), "--shapes", "tiny", "--steps", "1",
-                        "--warmup", "0", "--max-tokens", "32", "--results-dir", ""],
+                        "--warmup", "0", "--max-tokens", "32", "--full", "--results-dir", ""],
                        cwd=ROOT, capture_output=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     d = json.loads([ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")][0])
