@@ -83,8 +83,11 @@ struct SubTile {
     }
   }
 
+  // LOWER: keys below `begin` are masked too (a sliding window's first sub-tile; callers skip the
+  // sub-tiles that lie wholly below the window instead of masking them)
+  template <bool LOWER = false>
   __device__ __forceinline__ void compute(int kbase, int end, int lane, char* vbuf, float scale_log2,
-                                          bf16x8 (&kf)[2][KS], u32x4 (&vst)[NV]) {
+                                          bf16x8 (&kf)[2][KS], u32x4 (&vst)[NV], int begin = 0) {
     const int g4 = lane >> 4;
     // ---- S^T = K . Q^T ----
     f32x4 s[2];
@@ -108,7 +111,8 @@ struct SubTile {
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int key = kbase + kt * 16 + 4 * g4 + i;
-        const float v = key < end ? s[kt][i] * scale_log2 : kNegInfM;
+        const bool vis = LOWER ? key < end && key >= begin : key < end;
+        const float v = vis ? s[kt][i] * scale_log2 : kNegInfM;
         s[kt][i] = v;
         mx = fmaxf(mx, v);
       }

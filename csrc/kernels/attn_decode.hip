@@ -34,29 +34,41 @@
 // polling mergers that waited on unscheduled producers cost the 3-engine bench 8-20 %). The tag is
 // a per-(row, kv head) epoch in device memory the merger advances (tag = epoch + 1: never 0,
 // never reused), so a granule left by any earlier launch can never match. Spins are bounded.
+//
+// Sliding window (window = W > 0; 0 = every key): the token at position L - 1 attends keys
+// [lo, L), lo = max(0, L - W). The split form balances its blocks over [lo & ~31, L) (sub-tiles stay
+// 32-key aligned) and masks the keys below lo in the first sub-tile. The fused form keeps its fixed
+// chunks: the blocks of chunks below lo / chunk exit at once, the others publish / merge as the
+// live chunks 0 .. ceil(L / chunk) - lo / chunk - 1, and a wave or sub-tile wholly below lo is
+// skipped like the ones past L. W >= L is the unwindowed arithmetic. The windowed kernels are
+// instantiations of their own (WIN), so a launch without a window runs the code it always ran.
 #include "attn_core.h"
 
 namespace llmc {
 
 // ---------------------------------------------------------------------------------------------
 // One block of the split form: chunk c (of a grid of `gridc` per head) of kv head kvh, row b.
-template <int G, int D, int NW>
+template <int G, int D, int NW, bool WIN>
 __device__ __forceinline__ void attn_split_block(
     int c, int kvh, int b, int gridc, const bf16_t* __restrict__ q, int q_stride, const bf16_t* __restrict__ k_cache,
     const bf16_t* __restrict__ v_cache, const int32_t* __restrict__ block_tables, int bt_stride,
     const int32_t* __restrict__ seq_lens, float* __restrict__ part, int* __restrict__ counters, bf16_t* __restrict__ out,
     int out_stride, int nkv, int bs, int nblocks, int min_chunk, int max_chunks, int gsize, int max_groups,
-    float scale_log2, int* __restrict__ fault, char* smem) {
+    float scale_log2, int* __restrict__ fault, int window, char* smem) {
   static_assert(G <= 16 && D % 32 == 0 && D <= 128, "shape");
   using ST = SubTile<G, D>;
   constexpr int NT = NW * 64;
   int* ctr = counters + (b * nkv + kvh) * (2 + max_groups) * kCtrPitch;  // {ticket, epoch, group tickets}
   const uint32_t tag = static_cast<uint32_t>(__hip_atomic_load(ctr + kCtrPitch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) + 1u;
   const int L = seq_lens[b];
-  const int nchunks = decode_nsplit(L, gridc, -min_chunk);
+  const int lo = WIN ? max(0, L - window) : 0;  // first key of the window (WIN = false: all folds away)
+  const int lo32 = lo & ~31;
+  const int nchunks = decode_nsplit(L - lo32, gridc, -min_chunk);
   if (c >= nchunks) return;
   int start, end;
-  decode_range(L, nchunks, c, -min_chunk, start, end);
+  decode_range(L - lo32, nchunks, c, -min_chunk, start, end);
+  start += lo32;
+  end += lo32;
 
   const int tid = threadIdx.x, wave = tid / 64, lane = tid % 64;
   char* vbuf = smem + wave * 32 * kVRowBytes;  // per-wave V image [32][256 B]
@@ -89,7 +101,8 @@ __device__ __forceinline__ void attn_split_block(
   for (int k0 = wbase;; k0 += 64) {
     if (!valid(k0)) break;
     if (valid(k0 + 32)) st.issue(k0 + 32, end, lane, row, k_cache, v_cache, kfB, vsB);
-    st.compute(k0, end, lane, vbuf, scale_log2, kfA, vsA);
+    // only the block's first sub-tile holds keys below lo (lo - lo32 < 32), never all of it
+    st.template compute<WIN>(k0, end, lane, vbuf, scale_log2, kfA, vsA, lo);
     if (!valid(k0 + 32)) break;
     if (valid(k0 + 64)) st.issue(k0 + 64, end, lane, row, k_cache, v_cache, kfA, vsA);
     st.compute(k0 + 32, end, lane, vbuf, scale_log2, kfB, vsB);
@@ -105,27 +118,27 @@ __device__ __forceinline__ void attn_split_block(
                               reinterpret_cast<int*>(pages), tid, fault);
 }
 
-template <int G, int D, int NW>
+template <int G, int D, int NW, bool WIN>
 __global__ __launch_bounds__(NW * 64) void attn_decode_split_kernel(
     const bf16_t* __restrict__ q, int q_stride, const bf16_t* __restrict__ k_cache,
     const bf16_t* __restrict__ v_cache, const int32_t* __restrict__ block_tables, int bt_stride,
     const int32_t* __restrict__ seq_lens, float* __restrict__ part, int* __restrict__ counters, bf16_t* __restrict__ out,
     int out_stride, int nkv, int bs, int nblocks, int min_chunk, int max_chunks, int gsize, int max_groups,
-    float scale_log2, int* __restrict__ fault) {
+    float scale_log2, int* __restrict__ fault, int window) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  attn_split_block<G, D, NW>(blockIdx.x, blockIdx.y, blockIdx.z, gridDim.x, q, q_stride, k_cache, v_cache, block_tables,
-                             bt_stride, seq_lens, part, counters, out, out_stride, nkv, bs, nblocks, min_chunk, max_chunks,
-                             gsize, max_groups, scale_log2, fault, smem);
+  attn_split_block<G, D, NW, WIN>(blockIdx.x, blockIdx.y, blockIdx.z, gridDim.x, q, q_stride, k_cache, v_cache, block_tables,
+                                  bt_stride, seq_lens, part, counters, out, out_stride, nkv, bs, nblocks, min_chunk,
+                                  max_chunks, gsize, max_groups, scale_log2, fault, window, smem);
 }
 
 // ---------------------------------------------------------------------------------------------
-template <int G, int D>
+template <int G, int D, bool WIN>
 __global__ __launch_bounds__(256) void attn_decode_fused_kernel(
     const bf16_t* __restrict__ q, int q_stride, const bf16_t* __restrict__ k_cache,
     const bf16_t* __restrict__ v_cache, const int32_t* __restrict__ block_tables, int bt_stride,
     const int32_t* __restrict__ seq_lens, float* __restrict__ part, int* __restrict__ counters,
     bf16_t* __restrict__ out, int out_stride, int nkv, int bs, int nblocks, int chunk, int max_chunks, int gsize,
-    int max_groups, float scale_log2, int* __restrict__ fault) {
+    int max_groups, float scale_log2, int* __restrict__ fault, int window) {
   static_assert(G <= 16 && D % 32 == 0 && D <= 128, "shape");
   using ST = SubTile<G, D>;
   const int c = blockIdx.x, kvh = blockIdx.y, b = blockIdx.z;
@@ -142,22 +155,29 @@ __global__ __launch_bounds__(256) void attn_decode_fused_kernel(
   const uint32_t tag = static_cast<uint32_t>(__hip_atomic_load(ctr + kCtrPitch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) + 1u;
   ST st;
   st.init(q + static_cast<int64_t>(b) * q_stride + kvh * G * D, lane);
-  if (c * chunk >= L) return;  // block-uniform
-  const int nchunks = (L + chunk - 1) / chunk;
+  const int lo = WIN ? max(0, L - window) : 0;     // first key of the window
+  const int c0 = WIN ? lo >> (chunk == 256 ? 8 : 7) : 0;  // first live chunk (chunk is 128 or 256)
+  // block-uniform; a chunk below the window takes no ticket and publishes nothing
+  if (c * chunk >= L || (WIN && c < c0)) return;
+  const int nchunks = (L + chunk - 1) / chunk - c0;  // live chunks: c - c0 of them is this block
   const int end = min(L, key0 + per_wave);
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* vbuf = smem + wave * 32 * kVRowBytes;
   float* red = reinterpret_cast<float*>(smem + 4 * 32 * kVRowBytes);
-  if (key0 < L) {  // wave-uniform
+  // wave-uniform: the wave's first / second 32 keys hold a key of [lo, L). Sub-tiles wholly below
+  // the window are skipped like the ones past L (the chunk's wave that holds lo is always live).
+  const bool liveA = key0 < L && (!WIN || key0 + 32 > lo);
+  const bool liveB = key0 + 32 < end && (!WIN || key0 + per_wave > lo);
+  if (WIN ? liveA || liveB : liveA) {
     const int64_t base = (static_cast<int64_t>(page) * nkv + kvh) * bs * D;
     auto row = [&](const bf16_t* cache, int key) { return cache + base + static_cast<int64_t>(key % bs) * D; };
     bf16x8 kfA[2][ST::KS], kfB[2][ST::KS];
     u32x4 vsA[ST::NV], vsB[ST::NV];
-    st.issue(key0, end, lane, row, k_cache, v_cache, kfA, vsA);
-    if (key0 + 32 < end) st.issue(key0 + 32, end, lane, row, k_cache, v_cache, kfB, vsB);
-    st.compute(key0, end, lane, vbuf, scale_log2, kfA, vsA);
-    if (key0 + 32 < end) st.compute(key0 + 32, end, lane, vbuf, scale_log2, kfB, vsB);
+    if (!WIN || liveA) st.issue(key0, end, lane, row, k_cache, v_cache, kfA, vsA);
+    if (liveB) st.issue(key0 + 32, end, lane, row, k_cache, v_cache, kfB, vsB);
+    if (!WIN || liveA) st.template compute<WIN>(key0, end, lane, vbuf, scale_log2, kfA, vsA, lo);
+    if (liveB) st.template compute<WIN>(key0 + 32, end, lane, vbuf, scale_log2, kfB, vsB, lo);
   }
   st.to_lds(red, wave, lane);
   __syncthreads();
@@ -166,7 +186,7 @@ __global__ __launch_bounds__(256) void attn_decode_fused_kernel(
     store_direct<G, D, 4>(red, out_row, tid);
     return;
   }
-  publish_and_merge<G, D, 4>(red, part, ctr, b, nkv, kvh, c, nchunks, gsize, max_chunks, max_groups, tag, out_row, smem,
+  publish_and_merge<G, D, 4>(red, part, ctr, b, nkv, kvh, c - c0, nchunks, gsize, max_chunks, max_groups, tag, out_row, smem,
                              reinterpret_cast<int*>(red + 4 * G * (D + 2)), tid, fault);
 }
 
@@ -178,21 +198,22 @@ template <int G, int D, int NW>
 static int launch_split_nw(dim3 grid, hipStream_t s, const void* q, int q_stride, const void* kc, const void* vc,
                            const void* bt, int bt_stride, const void* sl, void* part, void* ctr, void* out,
                            int out_stride, int nkv, int bs, int nblocks, int chunk, int max_chunks, int gsize,
-                           int max_groups, int max_chunk_keys, float scale, int* fault) {
+                           int max_groups, int max_chunk_keys, float scale, int* fault, int window) {
   const size_t lds = NW * 32 * kVRowBytes + static_cast<size_t>(NW) * G * (D + 2) * sizeof(float) +
                      static_cast<size_t>((max_chunk_keys + bs - 1) / bs + 2) * sizeof(int);
   if (lds > 160 * 1024) return -4;
-  auto kern = attn_decode_split_kernel<G, D, NW>;
-  static bool attr_set = false;
-  if (!attr_set) {
+  // the windowed kernels are instantiations of their own: window = 0 runs the code it always ran
+  auto kern = window > 0 ? attn_decode_split_kernel<G, D, NW, true> : attn_decode_split_kernel<G, D, NW, false>;
+  static bool attr_set[2] = {false, false};
+  if (!attr_set[window > 0]) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                               160 * 1024);
-    attr_set = true;
+    attr_set[window > 0] = true;
   }
   kern<<<grid, NW * 64, lds, s>>>((const bf16_t*)q, q_stride, (const bf16_t*)kc, (const bf16_t*)vc,
                                   (const int32_t*)bt, bt_stride, (const int32_t*)sl, (float*)part, (int*)ctr,
                                   (bf16_t*)out, out_stride, nkv, bs, nblocks, chunk, max_chunks, gsize, max_groups,
-                                  scale * 1.4426950408889634f, fault);
+                                  scale * 1.4426950408889634f, fault, window);
   return static_cast<int>(hipGetLastError());
 }
 
@@ -200,7 +221,7 @@ template <int G, int D>
 static int launch_split(dim3 grid, hipStream_t s, const void* q, int q_stride, const void* kc, const void* vc,
                         const void* bt, int bt_stride, const void* sl, void* part, void* ctr, void* out, int out_stride,
                         int nkv, int bs, int nblocks, int chunk, int max_chunks, int gsize, int max_groups,
-                        float scale, int* fault) {
+                        float scale, int* fault, int window) {
   // page-id staging sized for the largest balanced range any sequence of this table can get
   const int grid_chunks = static_cast<int>(grid.x);
   const int units = (bt_stride * bs + 31) / 32;
@@ -210,22 +231,23 @@ static int launch_split(dim3 grid, hipStream_t s, const void* q, int q_stride, c
   // 8 waves, so a row's per-wave key partition never depends on the bucket its batch selected
   if (G > 1 && (bal >= 512 || chunk >= 512))
     return launch_split_nw<G, D, 8>(grid, s, q, q_stride, kc, vc, bt, bt_stride, sl, part, ctr, out, out_stride, nkv,
-                                    bs, nblocks, chunk, max_chunks, gsize, max_groups, max_chunk, scale, fault);
+                                    bs, nblocks, chunk, max_chunks, gsize, max_groups, max_chunk, scale, fault, window);
   return launch_split_nw<G, D, 4>(grid, s, q, q_stride, kc, vc, bt, bt_stride, sl, part, ctr, out, out_stride, nkv, bs,
-                                  nblocks, chunk, max_chunks, gsize, max_groups, max_chunk, scale, fault);
+                                  nblocks, chunk, max_chunks, gsize, max_groups, max_chunk, scale, fault, window);
 }
 
 template <int G, int D>
 static int launch_fused(dim3 grid, hipStream_t s, const void* q, int q_stride, const void* kc, const void* vc,
                         const void* bt, int bt_stride, const void* sl, void* part, void* ctr, void* out, int out_stride,
                         int nkv, int bs, int nblocks, int chunk, int max_chunks, int gsize, int max_groups,
-                        float scale, int* fault) {
+                        float scale, int* fault, int window) {
   const size_t lds = 4 * 32 * kVRowBytes + static_cast<size_t>(4) * G * (D + 2) * sizeof(float) + 16;  // + flag
   if (lds > 64 * 1024) return -4;
-  attn_decode_fused_kernel<G, D><<<grid, 256, lds, s>>>(
+  auto kern = window > 0 ? attn_decode_fused_kernel<G, D, true> : attn_decode_fused_kernel<G, D, false>;
+  kern<<<grid, 256, lds, s>>>(
       (const bf16_t*)q, q_stride, (const bf16_t*)kc, (const bf16_t*)vc, (const int32_t*)bt, bt_stride,
       (const int32_t*)sl, (float*)part, (int*)ctr, (bf16_t*)out, out_stride, nkv, bs, nblocks, chunk, max_chunks, gsize,
-      max_groups, scale * 1.4426950408889634f, fault);
+      max_groups, scale * 1.4426950408889634f, fault, window);
   return static_cast<int>(hipGetLastError());
 }
 
@@ -233,13 +255,13 @@ template <int G>
 static int launch_g(bool fused, int D, dim3 grid, hipStream_t s, const void* q, int q_stride, const void* kc,
                     const void* vc, const void* bt, int bt_stride, const void* sl, void* part, void* ctr, void* out,
                     int out_stride, int nkv, int bs, int nblocks, int chunk, int max_chunks, int gsize,
-                    int max_groups, float scale, int* fault) {
+                    int max_groups, float scale, int* fault, int window) {
 #define LLMC_ATTN_D(DD)                                                                                          \
   case DD:                                                                                                       \
     return fused ? launch_fused<G, DD>(grid, s, q, q_stride, kc, vc, bt, bt_stride, sl, part, ctr, out, out_stride, \
-                                       nkv, bs, nblocks, chunk, max_chunks, gsize, max_groups, scale, fault)     \
+                                       nkv, bs, nblocks, chunk, max_chunks, gsize, max_groups, scale, fault, window) \
                  : launch_split<G, DD>(grid, s, q, q_stride, kc, vc, bt, bt_stride, sl, part, ctr, out, out_stride, \
-                                       nkv, bs, nblocks, chunk, max_chunks, gsize, max_groups, scale, fault);
+                                       nkv, bs, nblocks, chunk, max_chunks, gsize, max_groups, scale, fault, window);
   switch (D) {
     LLMC_ATTN_D(64)
     LLMC_ATTN_D(96)
@@ -263,6 +285,7 @@ using namespace llmc;
 // Chunk partials are merged in one level up to kAttnOneLevel chunks, else in groups of kAttnGroup.
 // fault (nullable int32): set to 1 when a merger gave up waiting for a partial (bounded spin): the
 // step's attention output is then invalid and the caller must fail the request.
+// window: 0 = every key; W > 0 = the keys [max(0, L - W), L) of each row (sliding window).
 
 extern "C" int llmc_attn_decode_groups(int max_chunks) {
   return max_chunks > kAttnOneLevel ? (max_chunks + kAttnGroup - 1) / kAttnGroup : 0;
@@ -272,7 +295,8 @@ extern "C" int llmc_attn_decode(const void* q, int q_stride, const void* k_cache
                                 const void* block_tables, int bt_stride, const void* seq_lens, void* part,
                                 void* counters, void* out, int out_stride, int B, int nh, int nkv, int D, int bs,
                                 int nblocks, int chunk, int grid_chunks, int max_chunks, float scale, int fused,
-                                void* fault, hipStream_t s) {
+                                void* fault, int window, hipStream_t s) {
+  if (window < 0) return -1;
   if (nh % nkv != 0 || grid_chunks > max_chunks || grid_chunks < 1 || nblocks < 1 || counters == nullptr ||
       bt_stride < 1)
     return -1;
@@ -284,10 +308,10 @@ extern "C" int llmc_attn_decode(const void* q, int q_stride, const void* k_cache
   dim3 grid(grid_chunks, nkv, B);
   const bool f = fused != 0;
   switch (G) {
-    case 1: return launch_g<1>(f, D, grid, s, q, q_stride, k_cache, v_cache, block_tables, bt_stride, seq_lens, part, counters, out, out_stride, nkv, bs, nblocks, chunk, max_chunks, gsize, max_groups, scale, static_cast<int*>(fault));
-    case 2: return launch_g<2>(f, D, grid, s, q, q_stride, k_cache, v_cache, block_tables, bt_stride, seq_lens, part, counters, out, out_stride, nkv, bs, nblocks, chunk, max_chunks, gsize, max_groups, scale, static_cast<int*>(fault));
-    case 4: return launch_g<4>(f, D, grid, s, q, q_stride, k_cache, v_cache, block_tables, bt_stride, seq_lens, part, counters, out, out_stride, nkv, bs, nblocks, chunk, max_chunks, gsize, max_groups, scale, static_cast<int*>(fault));
-    case 8: return launch_g<8>(f, D, grid, s, q, q_stride, k_cache, v_cache, block_tables, bt_stride, seq_lens, part, counters, out, out_stride, nkv, bs, nblocks, chunk, max_chunks, gsize, max_groups, scale, static_cast<int*>(fault));
+    case 1: return launch_g<1>(f, D, grid, s, q, q_stride, k_cache, v_cache, block_tables, bt_stride, seq_lens, part, counters, out, out_stride, nkv, bs, nblocks, chunk, max_chunks, gsize, max_groups, scale, static_cast<int*>(fault), window);
+    case 2: return launch_g<2>(f, D, grid, s, q, q_stride, k_cache, v_cache, block_tables, bt_stride, seq_lens, part, counters, out, out_stride, nkv, bs, nblocks, chunk, max_chunks, gsize, max_groups, scale, static_cast<int*>(fault), window);
+    case 4: return launch_g<4>(f, D, grid, s, q, q_stride, k_cache, v_cache, block_tables, bt_stride, seq_lens, part, counters, out, out_stride, nkv, bs, nblocks, chunk, max_chunks, gsize, max_groups, scale, static_cast<int*>(fault), window);
+    case 8: return launch_g<8>(f, D, grid, s, q, q_stride, k_cache, v_cache, block_tables, bt_stride, seq_lens, part, counters, out, out_stride, nkv, bs, nblocks, chunk, max_chunks, gsize, max_groups, scale, static_cast<int*>(fault), window);
     default: return -3;
   }
 }

@@ -31,6 +31,13 @@
 // rank's single kv head = 32-128 blocks), the long row-tile groups' key ranges are cut into 2-4
 // ranges on their own blocks; each writes (unnormalised O, m, l) in f32 and the last to finish merges
 // them in split order (deterministic).
+//
+// Sliding window (WIN instantiations, window = W > 0): the row at position p attends keys
+// (p - W, p]. A block starts staging at the first tile its earliest row tile needs, a wave skips the
+// tiles that end at or below its first row's lower bound, and the tiles that straddle some row's
+// lower bound (wave-uniform flag, like `diag`) take the masked path with both bounds; interior tiles
+// keep the unmasked path. 8- and 4-wave forms without a KV split; the launcher refuses the others.
+// The W = 0 instantiations carry none of it.
 #include <stdlib.h>
 
 #include <algorithm>
@@ -63,13 +70,13 @@ __device__ __forceinline__ uint32_t cvt_pk_bf16(float lo, float hi) {
 __device__ __forceinline__ int k_swz(int row, int ch) { return row * kRowBytes + ((ch ^ (row & 15)) << 4); }
 __device__ __forceinline__ int v_swz(int row, int ch) { return row * kRowBytes + ((ch ^ ((row & 3) << 2)) << 4); }
 
-template <int D, int WPB, int LA, bool P64, bool DMA = false>
+template <int D, int WPB, int LA, bool P64, bool DMA = false, bool WIN = false>
 __global__ __launch_bounds__(WPB * 64, 8 / WPB) void attn_prefill_kernel(
     const bf16_t* __restrict__ q, int q_stride, const bf16_t* __restrict__ k_cache, const bf16_t* __restrict__ v_cache,
     const int32_t* __restrict__ block_tables, int bt_stride, const int32_t* __restrict__ q_start,
     const int32_t* __restrict__ q_lens, const int32_t* __restrict__ ctx_lens, bf16_t* __restrict__ out,
     int out_stride, int nh, int nkv, int bs, float scale_log2, int ksplit, int kmin, float* __restrict__ part,
-    int* __restrict__ counters, int T_all, int mode) {
+    int* __restrict__ counters, int T_all, int mode, int window) {
   constexpr int CH = D / 8;            // 16-B chunks per row
   constexpr int NT = WPB * 64;
   constexpr int NL = (kKT * CH + NT - 1) / NT;  // staging chunks per thread per tensor
@@ -140,9 +147,14 @@ __global__ __launch_bounds__(WPB * 64, 8 / WPB) void attn_prefill_kernel(
   const int nsplit = ksplit > 1 ? min(ksplit, max(1, ntiles_all / kmin)) : 1;
   if (sp >= nsplit) return;
   // this block's key tiles: split sp of the group's [0, ntiles_all) (all of it without a split)
-  const int t_lo = sp * ntiles_all / nsplit, ntiles = (sp + 1) * ntiles_all / nsplit;
+  int t_lo = sp * ntiles_all / nsplit;
+  const int ntiles = (sp + 1) * ntiles_all / nsplit;
   const int wave_kend = wvalid ? first_pos + min(pb * 32 + 31, qlen - 1) + 1 : 0;
   const int wave_qpos0 = first_pos + pb * 32;  // smallest query position of this wave
+  // WIN (mode 0, unsplit): the wave's rows need keys [wave_klo, wave_kend); the block's earliest row
+  // tile (rt_base / G) sets the first tile staged (< ntiles: its own position is a key it needs)
+  const int wave_klo = WIN ? wave_qpos0 - window + 1 : 0;
+  if constexpr (WIN) t_lo = max(first_pos + (rt_base / G) * 32 - window + 1, 0) / kKT;
 
   // Q^T fragments (B operand): lane (r, hh) holds Q[qi][h*D + ks*16 + 8hh .. +8]
   bf16x8 qf[KS];
@@ -226,7 +238,7 @@ __global__ __launch_bounds__(WPB * 64, 8 / WPB) void attn_prefill_kernel(
   // one 64-key tile of every wave (kb / vb: the tile's K and V images in LDS)
   auto tile_compute = [&](int t, const char* kb, const char* vb) {
       const int kt = t * kKT;
-      if (wvalid && kt < wave_kend) {
+      if (wvalid && kt < wave_kend && (!WIN || kt + kKT > wave_klo)) {
         // ---- S^T = K . Q^T for two 32-key halves ----
         f32x16 s[2];
   #pragma unroll
@@ -248,16 +260,28 @@ __global__ __launch_bounds__(WPB * 64, 8 / WPB) void attn_prefill_kernel(
         // relative rounding), which leaves the O rescale out of almost every tile; P packed by
         // v_cvt_pk_bf16_f32 (two floats per instruction, RNE).
         const bool diag = kt + kKT - 1 > wave_qpos0;  // wave-uniform
+        // WIN: the tile holds a key at or below some row's lower bound (the wave's last row has the
+        // highest: wave_kend - window); wave-uniform. Never with window >= ctx.
+        const bool lowm = WIN && kt < wave_kend - window;
         float mx = -1e30f;
         // diag: score (kb2, i) is key kt + 4 hh + kb2*32 + (i & 3) + 8 (i >> 2): visible iff that
         // compile-time offset <= lim (an inline-constant compare, no per-score add)
         const int lim = qpos - kt - 4 * hh;
-        if (diag) {
+        // WIN: visible iff lim - window < offset <= lim, as ONE unsigned compare per score
+        // (offset - lim_lo1 < window; the window is clamped to 2^30, so nothing wraps): one mask per
+        // score as in the causal compare, not two and their AND
+        const int lim_lo1 = lim - window + 1;
+        const unsigned uwin = static_cast<unsigned>(window);
+        // WIN kernels take the one masked path on diagonal tiles too (there every row's lower bound
+        // lies below the tile, lim_lo1 <= 0, so the compare is the causal one). A row with no
+        // visible key in a tile keeps mx = -1e30: its p are all 0 and its state stays finite.
+        auto vis = [&](int off) { return WIN ? static_cast<unsigned>(off - lim_lo1) < uwin : off <= lim; };
+        if (diag || lowm) {
   #pragma unroll
           for (int kb2 = 0; kb2 < 2; ++kb2)
   #pragma unroll
             for (int i = 0; i < 16; ++i)
-              mx = fmaxf(mx, kb2 * 32 + (i & 3) + 8 * (i >> 2) <= lim ? s[kb2][i] : -1e30f);
+              mx = fmaxf(mx, vis(kb2 * 32 + (i & 3) + 8 * (i >> 2)) ? s[kb2][i] : -1e30f);
         } else {
   #pragma unroll
           for (int kb2 = 0; kb2 < 2; ++kb2)
@@ -269,12 +293,12 @@ __global__ __launch_bounds__(WPB * 64, 8 / WPB) void attn_prefill_kernel(
         const float m_new = mx_s > m_run + kSlack ? mx_s : m_run;
         const float neg_m = -m_new;
         float rs2[4] = {0.f, 0.f, 0.f, 0.f};
-        if (diag) {
+        if (diag || lowm) {
   #pragma unroll
           for (int kb2 = 0; kb2 < 2; ++kb2)
   #pragma unroll
             for (int i = 0; i < 16; ++i) {
-              const float p = kb2 * 32 + (i & 3) + 8 * (i >> 2) <= lim
+              const float p = vis(kb2 * 32 + (i & 3) + 8 * (i >> 2))
                                   ? __builtin_amdgcn_exp2f(fmaf(s[kb2][i], scale_log2, neg_m))
                                   : 0.f;
               s[kb2][i] = p;
@@ -695,7 +719,9 @@ extern "C" int llmc_attn_prefill(const void* q, int q_stride, const void* k_cach
                                  const void* block_tables, int bt_stride, const void* q_start, const void* q_lens,
                                  const void* ctx_lens, void* out, int out_stride, int B, int max_qlen, int nh, int nkv,
                                  int D, int bs, float scale, int ksplit, int kmin, void* part, void* counters,
-                                 int T_all, int form_arg, hipStream_t s) {
+                                 int T_all, int form_arg, int window, hipStream_t s) {
+  if (window < 0) return -1;
+  window = std::min(window, 1 << 30);  // any window >= the context is the same; keeps qpos - window in range
   if (nh % nkv != 0 || ksplit < 1 || ksplit > kMaxSplit ||
       (ksplit > 1 && (part == nullptr || counters == nullptr || T_all < 1 || kmin < 1)))
     return -1;
@@ -712,6 +738,14 @@ extern "C" int llmc_attn_prefill(const void* q, int q_stride, const void* k_cach
   if (form_arg >= 0 && form_arg <= 3 && ksplit == 1) form = form_arg;
   if (form == 1 && (G > 4 || 8 % G != 0)) form = 0;  // pairs need WPB / G >= 2 row tiles
   if (form == 3 && !(D == 128 && bs == kKT)) form = 2;  // key halves: LDS-DMA staging only
+  if (window > 0) {
+    // the window is implemented by the 8- and 4-wave forms of an unsplit grid: a forced paired /
+    // key-halves form or a KV split is refused (never run unwindowed); the library's own choice of
+    // one of those becomes the 4-wave form, the other shortener of a one-round grid
+    const bool forced = (form_env >= 0 && form_env <= 3) || (form_arg >= 0 && form_arg <= 3);
+    if (ksplit > 1 || (forced && (form == 1 || form == 3))) return -5;
+    if (form == 1 || form == 3) form = 2;
+  }
   const int wpb = form == 2 ? 4 : 8, mode = form == 1 ? 1 : form == 3 ? 2 : 0;
   static const int dma_env = [] {
     // LDS-DMA K/V staging (64-key pages, D = 128, 8-wave blocks): 2-5 % faster on every measured
@@ -731,12 +765,17 @@ extern "C" int llmc_attn_prefill(const void* q, int q_stride, const void* k_cach
     if (bs == kKT) LLMC_PFP(DD, L, true);                                                                        \
     else LLMC_PFP(DD, L, false);                                                                                 \
   } while (0)
-#define LLMC_PFW(DD, L, P, W)                                                                                    \
-  attn_prefill_kernel<DD, W, L, P><<<grid, W * 64, 0, s>>>((const bf16_t*)q, q_stride, (const bf16_t*)k_cache,     \
-                                               (const bf16_t*)v_cache, (const int32_t*)block_tables, bt_stride,   \
-                                               (const int32_t*)q_start, (const int32_t*)q_lens,                  \
-                                               (const int32_t*)ctx_lens, (bf16_t*)out, out_stride, nh, nkv, bs, sl2, \
-                                               ksplit, kmin, (float*)part, (int*)counters, T_all, mode)
+#define LLMC_PFK(W, ...)                                                                                         \
+  __VA_ARGS__<<<grid, W * 64, 0, s>>>((const bf16_t*)q, q_stride, (const bf16_t*)k_cache, (const bf16_t*)v_cache,   \
+                                      (const int32_t*)block_tables, bt_stride, (const int32_t*)q_start,            \
+                                      (const int32_t*)q_lens, (const int32_t*)ctx_lens, (bf16_t*)out, out_stride,  \
+                                      nh, nkv, bs, sl2, ksplit, kmin, (float*)part, (int*)counters, T_all, mode,   \
+                                      window)
+#define LLMC_PFW(DD, L, P, W)                                        \
+  do {                                                               \
+    if (window > 0) LLMC_PFK(W, attn_prefill_kernel<DD, W, L, P, false, true>); \
+    else LLMC_PFK(W, attn_prefill_kernel<DD, W, L, P>);              \
+  } while (0)
 #define LLMC_PFP(DD, L, P)                         \
   do {                                             \
     if (L == 1 && wpb == 4) LLMC_PFW(DD, 1, P, 4); \
@@ -748,10 +787,8 @@ extern "C" int llmc_attn_prefill(const void* q, int q_stride, const void* k_cach
     else LLMC_PF(DD, 1);                       \
   } while (0)
   if (dma) {
-    attn_prefill_kernel<128, 8, 1, true, true><<<grid, 512, 0, s>>>(
-        (const bf16_t*)q, q_stride, (const bf16_t*)k_cache, (const bf16_t*)v_cache, (const int32_t*)block_tables,
-        bt_stride, (const int32_t*)q_start, (const int32_t*)q_lens, (const int32_t*)ctx_lens, (bf16_t*)out, out_stride,
-        nh, nkv, bs, sl2, ksplit, kmin, (float*)part, (int*)counters, T_all, mode);
+    if (window > 0) LLMC_PFK(8, attn_prefill_kernel<128, 8, 1, true, true, true>);
+    else LLMC_PFK(8, attn_prefill_kernel<128, 8, 1, true, true>);
     return static_cast<int>(hipGetLastError());
   }
   switch (D) {
@@ -764,5 +801,6 @@ extern "C" int llmc_attn_prefill(const void* q, int q_stride, const void* k_cach
 #undef LLMC_PF
 #undef LLMC_PFP
 #undef LLMC_PFW
+#undef LLMC_PFK
   return static_cast<int>(hipGetLastError());
 }

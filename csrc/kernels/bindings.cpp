@@ -45,12 +45,12 @@ int llmc_attn_oproj(const void*, const void*, const void*, const void*, int, con
                     int, const void* const*, void*, int, int, size_t, const void*, const void*, float, int, int,
                     void*, void*, void*, void*, hipStream_t);
 int llmc_attn_decode(const void*, int, const void*, const void*, const void*, int, const void*, void*, void*, void*,
-                     int, int, int, int, int, int, int, int, int, int, float, int, void*, hipStream_t);
+                     int, int, int, int, int, int, int, int, int, int, float, int, void*, int, hipStream_t);
 int llmc_gemv_qkv_rope(int, const void*, int, const void*, float, const void*, int, int, void*, int, void*, void*,
                        const void*, const void*, const void*, const void*, int, int, int, int, int, hipStream_t);
 int llmc_attn_prefill(const void*, int, const void*, const void*, const void*, int, const void*, const void*,
                       const void*, void*, int, int, int, int, int, int, int, float, int, int, void*, void*, int,
-                      int, hipStream_t);
+                      int, int, hipStream_t);
 int llmc_attn_prefill_form(int, int, int, int, int, int, int);
 int llmc_attn_prefill_plan(int, int, int, int, int, int, int, int*);
 int64_t llmc_attn_prefill_counters(int, int, int, int);
@@ -190,11 +190,15 @@ PYBIND11_MODULE(_llmc_hip, m) {
   });
   m.def("attn_decode", [](ptr q, int qs, ptr kc, ptr vc, ptr bt, int bts, ptr sl, ptr part, ptr ctr, ptr out, int os,
                           int B, int nh, int nkv, int D, int bs, int nblocks, int chunk, int grid_chunks,
-                          int max_chunks, float scale, int fused, ptr fault, ptr s) {
+                          int max_chunks, float scale, int fused, ptr fault, ptr s, int window) {
     check(llmc_attn_decode(P(q), qs, P(kc), P(vc), P(bt), bts, P(sl), P(part), P(ctr), P(out), os, B, nh, nkv, D, bs,
-                           nblocks, chunk, grid_chunks, max_chunks, scale, fused, P(fault), S(s)),
+                           nblocks, chunk, grid_chunks, max_chunks, scale, fused, P(fault), window, S(s)),
           "attn_decode");
-  });
+  }, py::arg("q"), py::arg("q_stride"), py::arg("k_cache"), py::arg("v_cache"), py::arg("block_tables"),
+     py::arg("bt_stride"), py::arg("seq_lens"), py::arg("part"), py::arg("counters"), py::arg("out"),
+     py::arg("out_stride"), py::arg("B"), py::arg("nh"), py::arg("nkv"), py::arg("D"), py::arg("bs"),
+     py::arg("nblocks"), py::arg("chunk"), py::arg("grid_chunks"), py::arg("max_chunks"), py::arg("scale"),
+     py::arg("fused"), py::arg("fault"), py::arg("stream"), py::arg("window") = 0);
   m.def("gemv_qkv_rope", [](int M, ptr x, int xs, ptr nw, float eps, ptr W, int N, int K, ptr qo, int qos, ptr kc,
                             ptr vc, ptr pos, ptr slots, ptr cos_t, ptr sin_t, int nh, int nkv, int D, int bs,
                             int mfma, ptr s) {
@@ -204,11 +208,15 @@ PYBIND11_MODULE(_llmc_hip, m) {
   });
   m.def("attn_prefill", [](ptr q, int qs, ptr kc, ptr vc, ptr bt, int bts, ptr qst, ptr ql, ptr cl, ptr out, int os,
                            int B, int max_qlen, int nh, int nkv, int D, int bs, float scale, int ksplit, int kmin,
-                           ptr part, ptr counters, int T, int form, ptr s) {
+                           ptr part, ptr counters, int T, int form, ptr s, int window) {
     check(llmc_attn_prefill(P(q), qs, P(kc), P(vc), P(bt), bts, P(qst), P(ql), P(cl), P(out), os, B, max_qlen, nh, nkv,
-                            D, bs, scale, ksplit, kmin, P(part), P(counters), T, form, S(s)),
+                            D, bs, scale, ksplit, kmin, P(part), P(counters), T, form, window, S(s)),
           "attn_prefill");
-  });
+  }, py::arg("q"), py::arg("q_stride"), py::arg("k_cache"), py::arg("v_cache"), py::arg("block_tables"),
+     py::arg("bt_stride"), py::arg("q_start"), py::arg("q_lens"), py::arg("ctx_lens"), py::arg("out"),
+     py::arg("out_stride"), py::arg("B"), py::arg("max_qlen"), py::arg("nh"), py::arg("nkv"), py::arg("D"),
+     py::arg("bs"), py::arg("scale"), py::arg("ksplit"), py::arg("kmin"), py::arg("part"), py::arg("counters"),
+     py::arg("T"), py::arg("form"), py::arg("stream"), py::arg("window") = 0);
   m.def("attn_prefill_counters", [](int B, int max_qlen, int nh, int nkv) {
     return llmc_attn_prefill_counters(B, max_qlen, nh, nkv);
   });

@@ -83,6 +83,7 @@ def describe(name: str, tp: Optional[int] = None) -> Dict:
         "layers": c.n_layers, "hidden": c.hidden, "heads": c.n_heads, "kv_heads": c.n_kv_heads,
         "head_dim": c.head_dim, "intermediate": c.intermediate, "vocab": c.vocab,
         "experts": c.n_experts, "top_k": c.top_k_experts,
+        **({"sliding_window": c.sliding_window} if c.sliding_window else {}),
         **({"path": c.checkpoint} if c.checkpoint else {}),
     }
 

@@ -321,7 +321,11 @@ class Engine:
         # two launches)
         self.ao_chunks: List[int] = [0] * len(self.attn_buckets)
         self.ao_nc = 0
-        if (self.on_gpu and self.ecfg.attn_oproj and B == 1 and self.bs % 32 == 0
+        # sliding-window models: attn_oproj and qkv_attn do not implement the window, so every
+        # bucket keeps qkv_rope + attn_decode + o_proj. A window no sequence of this engine can
+        # outgrow (W >= the longest context) masks nothing: such an engine runs unwindowed.
+        self.window = int(c.sliding_window) if 0 < c.sliding_window < ctxmax else 0
+        if (self.on_gpu and self.ecfg.attn_oproj and B == 1 and self.bs % 32 == 0 and not self.window
                 and (self.tp.size == 1 or self.ecfg.tp_attn_oproj)):
             self.ao_nc = ops.attn_oproj_grid(c.hidden, self.nh, self.nkv, self.D)
             if self.ao_nc:
@@ -336,7 +340,8 @@ class Engine:
         # their steps). Default: the fused-form buckets of short-qkv shards where attn_oproj does not
         # run; "all": every bucket, ahead of attn_oproj, the long ones as 256-key chunks
         self.qa_plan: List[Optional[tuple]] = [None] * len(self.attn_buckets)
-        if self.on_gpu and B == 1 and ops.qkv_attn_supported(self.nh, self.nkv, self.D, c.hidden):
+        if (self.on_gpu and B == 1 and not self.window
+                and ops.qkv_attn_supported(self.nh, self.nkv, self.D, c.hidden)):
             self.qa_plan, self.ao_chunks = qkv_attn_plan(self.attn_buckets, self.ao_chunks, str(self.ecfg.qkv_attn),
                                                          (self.nh + 2 * self.nkv) * self.D, self.bs)
             if any(self.qa_plan):
@@ -464,7 +469,8 @@ class Engine:
         bt = self._block_table([s for s, _ in batch])
         max_qlen = max(q_lens)
         max_ctx = max(ctx_lens)
-        ksplit, kmin = (ops.attn_prefill_plan(len(batch), max_qlen, max_ctx, self.nh, self.nkv, D=self.D, bs=self.bs)
+        ksplit, kmin = (ops.attn_prefill_plan(len(batch), max_qlen, max_ctx, self.nh, self.nkv, D=self.D, bs=self.bs,
+                                              window=self.window)
                         if ids_d.is_cuda else (1, 1))
         pws = (ops.attn_prefill_workspace(ksplit, T, self.nh, self.D, dev, len(batch), self.nkv, max_qlen)
                if ksplit > 1 else None)
@@ -491,7 +497,7 @@ class Engine:
                               self.nh, self.nkv, self.D, self.bs, qbuf)
             ops.attn_prefill(qbuf, self.k_cache[li], self.v_cache[li], bt, qs_d, ql_d, cl_d, attn, max_qlen,
                              self.nh, self.nkv, self.D, self.bs, self.scale, max_ctx=max_ctx, ksplit=ksplit, kmin=kmin,
-                             ws=pws)
+                             ws=pws, window=self.window)
             if sp is not None:
                 self._sp_row_parallel(lambda out: ops.linear(attn, Lw.w_o, EPI_RESADD, out=out), hs, pbuf, T)
                 if c.is_moe and self.w.ep:
@@ -709,7 +715,7 @@ class Engine:
                 else:
                     ops.attn_decode(q, self.k_cache[li], self.v_cache[li], self.block_tables[:B], self.seq_lens[:B],
                                     attn, part[:B], self.attn_counters[:B], self.nh, self.nkv, self.D, self.bs, chunk,
-                                    self.scale, grid_chunks, fused=fused, fault=self.attn_fault)
+                                    self.scale, grid_chunks, fused=fused, fault=self.attn_fault, window=self.window)
                     self._row_parallel(attn, Lw.w_o, h)
             if c.is_moe:
                 self._moe_decode(h, Lw, B, routed)

@@ -5,9 +5,11 @@ The reference has no local models at all: every "model" is a remote API (``inter
 Here a directory in Hugging Face layout becomes a first-class catalog family
 (``--weights-dir``), served by the same engine and kernels as the random-init architectures:
 
-* ``config_from_hf(dir)`` maps ``config.json`` (model_type llama / mixtral / phi3) to a
-  :class:`ModelConfig` (Llama-3.1 ``rope_scaling`` included) that records the checkpoint path and
-  the tokenizer's BOS / EOS ids;
+* ``config_from_hf(dir)`` maps ``config.json`` (model_type llama / mistral / mixtral / phi3; a
+  Mistral checkpoint has the Llama layer layout) to a :class:`ModelConfig` (Llama-3.1
+  ``rope_scaling`` included) that records the checkpoint path and the tokenizer's BOS / EOS ids. A
+  ``sliding_window`` shorter than the context becomes ``ModelConfig.sliding_window`` (one window for
+  every layer: Mistral-7B, Phi-3-mini-4k);
 * :class:`HFCheckpoint` reads tensors lazily (``safetensors.safe_open``; nothing is unpickled) and
   returns them in the engine's *logical* layout (``models/transformer.py``): fused Q|K|V rows,
   gate/up rows interleaved; the caller applies the head pair-interleave and the TP slice, so a
@@ -15,8 +17,8 @@ Here a directory in Hugging Face layout becomes a first-class catalog family
   (``block_sparse_moe.experts.{e}.w1/w2/w3``) and the fused one written by transformers 5
   (``mlp.experts.gate_up_proj``) are understood.
 
-Unsupported checkpoint features (attention/MLP biases, sliding windows shorter than the context,
-partial rotary, LongRoPE) raise :class:`CheckpointError` instead of running a wrong model.
+Unsupported checkpoint features (attention/MLP biases, per-layer sliding windows (``layer_types`` /
+``max_window_layers`` that differ between layers), partial rotary, LongRoPE) raise :class:`CheckpointError` instead of running a wrong model.
 """
 
 from __future__ import annotations
@@ -54,9 +56,9 @@ def config_from_hf(path: str, name: Optional[str] = None) -> ModelConfig:
     """ModelConfig of the Hugging Face checkpoint directory ``path``."""
     hc = _read_json(os.path.join(path, "config.json"))
     mt = hc.get("model_type", "")
-    arch = {"llama": "llama", "mixtral": "mixtral", "phi3": "phi3"}.get(mt)
+    arch = {"llama": "llama", "mistral": "llama", "mixtral": "mixtral", "phi3": "phi3"}.get(mt)
     if arch is None:
-        raise CheckpointError(f"{path}: model_type {mt!r} not supported (llama, mixtral, phi3)")
+        raise CheckpointError(f"{path}: model_type {mt!r} not supported (llama, mistral, mixtral, phi3)")
     if hc.get("attention_bias") or hc.get("mlp_bias"):
         raise CheckpointError(f"{path}: attention/MLP biases are not supported")
     if float(hc.get("partial_rotary_factor", 1.0)) != 1.0:
@@ -65,9 +67,26 @@ def config_from_hf(path: str, name: Optional[str] = None) -> ModelConfig:
     hidden = int(hc["hidden_size"])
     head_dim = int(hc.get("head_dim") or hidden // heads)
     max_pos = int(hc.get("max_position_embeddings", 8192))
-    sw = hc.get("sliding_window")
-    if sw is not None and int(sw) < max_pos:
-        raise CheckpointError(f"{path}: sliding-window attention ({sw}) is not supported")
+    n_layers = int(hc["num_hidden_layers"])
+    sw = int(hc.get("sliding_window") or 0)
+    window = sw if 0 < sw < max_pos else 0
+    if hc.get("use_sliding_window") is False:
+        window = 0
+    # only one window for every layer: layer_types / max_window_layers may make it per-layer
+    lt = hc.get("layer_types")
+    if lt:
+        if len(set(lt)) > 1:
+            raise CheckpointError(f"{path}: per-layer attention types ({sorted(set(lt))}) are not supported")
+        if lt[0] == "full_attention":
+            window = 0
+        elif lt[0] != "sliding_attention":
+            raise CheckpointError(f"{path}: attention layer type {lt[0]!r} is not supported")
+    elif window and hc.get("max_window_layers") is not None:
+        mwl = int(hc["max_window_layers"])  # layers [mwl, n_layers) slide
+        if 0 < mwl < n_layers:
+            raise CheckpointError(f"{path}: a sliding window on layers {mwl}.. only is not supported")
+        if mwl >= n_layers:
+            window = 0
     rp = hc.get("rope_parameters") or {}
     theta = float(hc.get("rope_theta") or rp.get("rope_theta") or 10000.0)
     rs_cfg = hc.get("rope_scaling") or (rp if rp.get("rope_type") not in (None, "default") else None)
@@ -87,7 +106,7 @@ def config_from_hf(path: str, name: Optional[str] = None) -> ModelConfig:
     return ModelConfig(
         name=name or os.path.basename(os.path.normpath(path)),
         arch=arch,
-        n_layers=int(hc["num_hidden_layers"]),
+        n_layers=n_layers,
         hidden=hidden,
         n_heads=heads,
         n_kv_heads=int(hc.get("num_key_value_heads") or heads),
@@ -105,6 +124,7 @@ def config_from_hf(path: str, name: Optional[str] = None) -> ModelConfig:
         bos_id=bos[0] if bos else -1,
         eos_ids=tuple(e for e in eos if 0 <= e < vocab),
         tie_embeddings=bool(hc.get("tie_word_embeddings", False)),
+        sliding_window=window,
     )
 
 

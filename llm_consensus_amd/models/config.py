@@ -44,6 +44,9 @@ class ModelConfig:
     bos_id: int = -1            # -1: the synthetic tokenizer's (vocab - 2)
     eos_ids: tuple = ()         # empty: the synthetic tokenizer's (vocab - 1)
     tie_embeddings: bool = False
+    # sliding-window attention: position p attends keys (p - W, p]; 0 = every key (one window for
+    # all layers)
+    sliding_window: int = 0
 
     @property
     def eos(self) -> tuple:
@@ -100,6 +103,8 @@ MIXTRAL_8X7B = ModelConfig("mixtral-8x7b", "mixtral", 32, 4096, 32, 8, 128, 1433
                            max_position=32768, n_experts=8, top_k_experts=2)
 PHI3_MINI = ModelConfig("phi-3-mini", "phi3", 32, 3072, 32, 32, 96, 8192, 32064, 10000.0,
                         max_position=4096)
+MISTRAL_7B = ModelConfig("mistral-7b", "llama", 32, 4096, 32, 8, 128, 14336, 32000, 10000.0,
+                         max_position=32768, sliding_window=4096)
 
 # Tiny variants: same code paths and kernel shape classes (GQA, d=128/96, MoE), small enough
 # for CPU tests and fast GPU numerics tests.
@@ -108,12 +113,15 @@ LLAMA_SMALL = ModelConfig("llama-small", "llama", 4, 1024, 8, 2, 128, 2816, 3200
 MIXTRAL_TINY = ModelConfig("mixtral-tiny", "mixtral", 2, 256, 4, 2, 64, 384, 1024, 1000000.0,
                            max_position=4096, n_experts=4, top_k_experts=2)
 PHI3_TINY = ModelConfig("phi3-tiny", "phi3", 2, 192, 2, 2, 96, 384, 1024, 10000.0, max_position=4096)
+# llama-tiny with a window short enough that tiny prompts cross it
+MISTRAL_TINY = LLAMA_TINY.with_(name="mistral-tiny", sliding_window=48)
 # tiny stand-in for Llama-3-70B in TP=4 rehearsals (heads, kv heads, FFN and vocab shard over 4)
 LLAMA_TINY_TP4 = ModelConfig("llama-tiny-tp4", "llama", 2, 512, 8, 4, 64, 1024, 1024, 500000.0, max_position=16384,
                              default_tp=4)
 
 FAMILIES = {c.name: c for c in (LLAMA3_8B, LLAMA3_70B, MIXTRAL_8X7B, PHI3_MINI,
-                                LLAMA_TINY, LLAMA_SMALL, MIXTRAL_TINY, PHI3_TINY, LLAMA_TINY_TP4)}
+                                LLAMA_TINY, LLAMA_SMALL, MIXTRAL_TINY, PHI3_TINY, LLAMA_TINY_TP4,
+                                MISTRAL_7B, MISTRAL_TINY)}
 
 
 def rope_inv_freq(cfg: ModelConfig):

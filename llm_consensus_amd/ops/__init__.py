@@ -257,15 +257,21 @@ def decode_attn_workspace(B, nh, nkv, D, max_chunks, device, fused: bool = False
 
 
 def attn_decode(q, k_cache, v_cache, block_tables, seq_lens, out, part, counters, nh, nkv, D, bs, chunk, scale,
-                grid_chunks: Optional[int] = None, fused: bool = False, fault: Optional[torch.Tensor] = None):
+                grid_chunks: Optional[int] = None, fused: bool = False, fault: Optional[torch.Tensor] = None,
+                window: int = 0):
     """Decode attention (K5), one launch. ``fused``: fixed ``chunk``-key blocks (128 or 256;
     ``grid_chunks`` = bucket capacity / chunk) — short contexts; else the balanced split over <=
     grid_chunks 8-wave blocks of >= ``chunk`` keys — long contexts. Both merge their partials in
     the same launch. ``part``/``counters`` come from ``decode_attn_workspace``. ``fault`` (int32
     [1], optional) is set to 1 by a merger that gave up waiting for a partial (bounded spin): the
-    output is then invalid (``Engine`` checks it after every decode and fails the request)."""
+    output is then invalid (``Engine`` checks it after every decode and fails the request).
+    ``window`` W > 0: sliding-window attention, a row of length L attends keys [max(0, L - W), L)
+    (0 = every key; W >= L is bit-identical to 0)."""
+    window = int(window)
+    if window < 0:
+        raise ValueError("attn_decode: window must be >= 0")
     if not q.is_cuda:
-        out.copy_(oracle.attn_decode(q, k_cache, v_cache, block_tables, seq_lens, nh, nkv, D, bs, scale))
+        out.copy_(oracle.attn_decode(q, k_cache, v_cache, block_tables, seq_lens, nh, nkv, D, bs, scale, window))
         return out
     B = q.shape[0]
     groups = counters.shape[-2] - 2
@@ -276,7 +282,8 @@ def attn_decode(q, k_cache, v_cache, block_tables, seq_lens, out, part, counters
         raise ValueError("attn_decode: workspace does not match (use decode_attn_workspace)")
     kernels().attn_decode(_p(q), q.stride(0), _p(k_cache), _p(v_cache), _p(block_tables), block_tables.stride(0),
                           _p(seq_lens), _p(part), _p(counters), _p(out), out.stride(0), B, nh, nkv, D, bs,
-                          k_cache.shape[0], chunk, gc, max_chunks, float(scale), 1 if fused else 0, _p(fault), _s(q))
+                          k_cache.shape[0], chunk, gc, max_chunks, float(scale), 1 if fused else 0, _p(fault), _s(q),
+                          window)
     return out
 
 
@@ -483,11 +490,15 @@ PREFILL_KSPLIT = int(os.environ.get("LLMC_PREFILL_KSPLIT", "-1"))
 PREFILL_KMIN = int(os.environ.get("LLMC_PREFILL_KMIN", "8"))
 
 
-def attn_prefill_plan(B, max_qlen, max_ctx, nh, nkv, ksplit=None, kmin=None, D=128, bs=64):
+def attn_prefill_plan(B, max_qlen, max_ctx, nh, nkv, ksplit=None, kmin=None, D=128, bs=64, window=0):
     """(ksplit, kmin) of a prefill attention launch (csrc/kernels/attn_prefill.hip): row-tile groups
     of >= 2 kmin key tiles run on min(ksplit, tiles // kmin) blocks; (1, _) = no split. ``D`` / ``bs``
-    (head dim, KV page size) tell the plan which unsplit block forms it competes against."""
+    (head dim, KV page size) tell the plan which unsplit block forms it competes against. With a
+    sliding ``window`` the plan never splits (the split grid does not implement it); an explicit
+    ``ksplit`` is passed on and ``attn_prefill`` raises."""
     k = PREFILL_KSPLIT if ksplit is None else int(ksplit)
+    if window > 0 and (ksplit is None or k < 0):
+        return 1, int(PREFILL_KMIN if kmin is None else kmin)
     if k < 0:
         return tuple(kernels().attn_prefill_plan(B, int(max_qlen), int(max_ctx), nh, nkv, int(D), int(bs)))
     return max(1, min(k, 4)), int(PREFILL_KMIN if kmin is None else kmin)
@@ -509,18 +520,28 @@ def attn_prefill_workspace(ksplit, T, nh, D, device, B=1, nkv=1, max_qlen=None):
 
 
 def attn_prefill(q, k_cache, v_cache, block_tables, q_start, q_lens, ctx_lens, out, max_qlen, nh, nkv, D, bs, scale,
-                 max_ctx=None, ksplit=None, kmin=None, ws=None, form=None):
+                 max_ctx=None, ksplit=None, kmin=None, ws=None, form=None, window: int = 0):
     """Causal paged prefill attention. ``max_ctx`` (default ``max_qlen``) feeds the KV-split plan;
     ``ksplit``/``kmin`` override it; ``ws`` is a caller-held attn_prefill_workspace reused across
     layers (it must not be shared by launches that can run concurrently); ``form`` forces the block
     form of an unsplit launch (0 = 8 waves, 1 = paired row tiles, 2 = 4 waves, 3 = key halves;
-    default: the kernel library's choice, ``kernels().attn_prefill_form``)."""
+    default: the kernel library's choice, ``kernels().attn_prefill_form``). ``window`` W > 0:
+    sliding-window attention, position p attends keys (p - W, p] (0 = every key <= p); implemented
+    by forms 0 and 2 without a KV split — a forced form 1 / 3 or ``ksplit`` > 1 raises. A window that
+    covers every context (W >= ``max_ctx``, which the caller then guarantees bounds ``ctx_lens``)
+    masks nothing and runs as the unwindowed launch, every form and the KV split included."""
+    window = int(window)
+    if window < 0:
+        raise ValueError("attn_prefill: window must be >= 0")
+    if max_ctx is not None and window >= max_ctx:
+        window = 0
     if not q.is_cuda:
         return oracle.attn_prefill(q, k_cache, v_cache, block_tables, q_start, q_lens, ctx_lens, nh, nkv, D, bs,
-                                   scale, out)
+                                   scale, out, window)
     B = q_lens.shape[0]
     T = q.shape[0]
-    k, km = attn_prefill_plan(B, max_qlen, max_qlen if max_ctx is None else max_ctx, nh, nkv, ksplit, kmin, D, bs)
+    k, km = attn_prefill_plan(B, max_qlen, max_qlen if max_ctx is None else max_ctx, nh, nkv, ksplit, kmin, D, bs,
+                               window)
     part = ctr = 0
     if k > 1:
         need_c = attn_prefill_counters(B, max_qlen, nh, nkv)
@@ -530,7 +551,8 @@ def attn_prefill(q, k_cache, v_cache, block_tables, q_start, q_lens, ctx_lens, o
     try:
         kernels().attn_prefill(_p(q), q.stride(0), _p(k_cache), _p(v_cache), _p(block_tables), block_tables.stride(0),
                                _p(q_start), _p(q_lens), _p(ctx_lens), _p(out), out.stride(0), B, int(max_qlen), nh,
-                               nkv, D, bs, float(scale), k, km, part, ctr, T, -1 if form is None else int(form), _s(q))
+                               nkv, D, bs, float(scale), k, km, part, ctr, T, -1 if form is None else int(form), _s(q),
+                               window)
     except Exception:
         # a failed launch may leave arrival counters armed; the next launch on this workspace
         # would merge before its partials arrived: re-zero them (stream-ordered)

@@ -92,7 +92,8 @@ def _gather_kv(cache, bt_row, L, bs):
     return cache[pages, :, (idx % bs)]
 
 
-def attn_decode(q, k_cache, v_cache, block_tables, seq_lens, nh, nkv, D, bs, scale):
+def attn_decode(q, k_cache, v_cache, block_tables, seq_lens, nh, nkv, D, bs, scale, window: int = 0):
+    """``window`` W > 0: the token at position L - 1 attends keys [max(0, L - W), L); 0 = all."""
     B = q.shape[0]
     G = nh // nkv
     out = torch.empty(B, nh * D, dtype=torch.bfloat16)
@@ -104,12 +105,16 @@ def attn_decode(q, k_cache, v_cache, block_tables, seq_lens, nh, nkv, D, bs, sca
         kk = k.repeat_interleave(G, dim=1)  # [L, nh, D]
         vv = v.repeat_interleave(G, dim=1)
         s = torch.einsum("hd,lhd->hl", qb, kk) * scale
+        if window > 0 and L > window:
+            s[:, : L - window] = float("-inf")
         p = torch.softmax(s, dim=-1)
         out[b] = torch.einsum("hl,lhd->hd", p, vv).reshape(-1).to(torch.bfloat16)
     return out
 
 
-def attn_prefill(q, k_cache, v_cache, block_tables, q_start, q_lens, ctx_lens, nh, nkv, D, bs, scale, out):
+def attn_prefill(q, k_cache, v_cache, block_tables, q_start, q_lens, ctx_lens, nh, nkv, D, bs, scale, out,
+                 window: int = 0):
+    """``window`` W > 0: position p attends keys (p - W, p]; 0 = every key <= p."""
     G = nh // nkv
     for b in range(len(q_lens)):
         ql, ctx, q0 = int(q_lens[b]), int(ctx_lens[b]), int(q_start[b])
@@ -122,6 +127,8 @@ def attn_prefill(q, k_cache, v_cache, block_tables, q_start, q_lens, ctx_lens, n
         qpos = torch.arange(ctx - ql, ctx, device=s.device).view(1, ql, 1)
         kpos = torch.arange(ctx, device=s.device).view(1, 1, ctx)
         s = s.masked_fill(kpos > qpos, float("-inf"))
+        if window > 0:
+            s = s.masked_fill(kpos <= qpos - window, float("-inf"))
         p = torch.softmax(s, dim=-1)
         o = torch.einsum("hqk,khd->qhd", p, v)
         out[q0:q0 + ql, : nh * D] = o.reshape(ql, nh * D).to(torch.bfloat16)
@@ -298,7 +305,10 @@ def reference_logits(w, cfg, ids, out_pos, cos_t: torch.Tensor, sin_t: torch.Ten
             q1 = min(T, q0 + attn_chunk)
             qc = q[q0:q1].view(q1 - q0, nkv, G, D)                        # [q, kv, G, D]
             s = torch.einsum("qkgd,tkd->kgqt", qc, k[:q1]) * scale         # keys 0..q1-1
-            mask = torch.arange(q1, device=dev).view(1, -1) > torch.arange(q0, q1, device=dev).view(-1, 1)
+            kpos, qpos = torch.arange(q1, device=dev).view(1, -1), torch.arange(q0, q1, device=dev).view(-1, 1)
+            mask = kpos > qpos
+            if cfg.sliding_window > 0:
+                mask = mask | (kpos <= qpos - cfg.sliding_window)
             s.masked_fill_(mask, float("-inf"))
             if p_bf16:
                 e = torch.exp(s - s.amax(-1, keepdim=True))
@@ -364,6 +374,8 @@ def reference_decode_layer(L, cfg, h_in: torch.Tensor, k_cache: torch.Tensor, v_
     k = torch.cat([k_old, k_new.unsqueeze(0)])
     v = torch.cat([v_old, v_new.unsqueeze(0)])
     s = torch.einsum("kgd,tkd->kgt", q, k) / math.sqrt(D)
+    if cfg.sliding_window > 0 and pos + 1 > cfg.sliding_window:
+        s[..., : pos + 1 - cfg.sliding_window] = float("-inf")
     if p_bf16:
         e = torch.exp(s - s.amax(-1, keepdim=True))
         o = torch.einsum("kgt,tkd->kgd", e.to(bf).float(), v) / e.sum(-1, keepdim=True)

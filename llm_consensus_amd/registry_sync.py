@@ -37,9 +37,13 @@ def _record(source: str, rid: str, cfg, raw: bool) -> dict:
            "kv_bytes_per_token_bf16": cfg.kv_bytes_per_token(), "default_tp": cfg.default_tp}
     if cfg.checkpoint:
         rec["path"] = cfg.checkpoint
+    if cfg.sliding_window:
+        rec["sliding_window"] = cfg.sliding_window
     if raw:
         d = dataclasses.asdict(cfg)
         d["eos_ids"] = list(d.get("eos_ids") or ())
+        if not d.get("sliding_window"):
+            d.pop("sliding_window", None)
         rec["raw"] = d
     return rec
 

@@ -1,6 +1,9 @@
 """Micro-benchmarks of individual decode kernels (device time via HIP events over many launches).
 
-Usage: python scripts/microbench_kernels.py [attn|gemv|all]
+Usage: python scripts/microbench_kernels.py [attn|gemv|all] [--window W]
+
+--window W: sliding-window attention (keys (p - W, p]) in the attn / attn-prefill cases;
+``attn-window`` prints windowed against unwindowed times side by side.
 """
 import math
 import os
@@ -12,6 +15,7 @@ import torch
 from llm_consensus_amd import ops
 
 BF = torch.bfloat16
+WINDOW = 0  # --window
 
 
 def timeit(fn, iters=50, warm=5):
@@ -72,7 +76,7 @@ def bench_attn(shapes=((32, 8, 128), (32, 32, 96), (16, 2, 128), (8, 1, 128), (4
                 gc = cap // ch
                 part, ctr = ops.decode_attn_workspace(1, nh, nkv, D, gc, "cuda", fused=True)
                 us = timeit(lambda: ops.attn_decode(q, kc, vc, bt, sl, out, part, ctr, nh, nkv, D, 64, ch, sc,
-                                                    grid_chunks=gc, fused=True))
+                                                    grid_chunks=gc, fused=True, window=WINDOW))
                 best = min(best, us)
                 line.append(f"fused c{ch} {us:6.2f}")
             for gc in [16, 32, 64, 128, 256]:
@@ -81,7 +85,7 @@ def bench_attn(shapes=((32, 8, 128), (32, 32, 96), (16, 2, 128), (8, 1, 128), (4
                     continue
                 part, ctr = ops.decode_attn_workspace(1, nh, nkv, D, gc_eff, "cuda")
                 us = timeit(lambda: ops.attn_decode(q, kc, vc, bt, sl, out, part, ctr, nh, nkv, D, 64, 128, sc,
-                                                    grid_chunks=gc_eff))
+                                                    grid_chunks=gc_eff, window=WINDOW))
                 best = min(best, us)
                 line.append(f"split g{gc_eff} {us:6.2f}")
             print(f"attn nh={nh} nkv={nkv} D={D} L={L:6d}: " + "  ".join(line)
@@ -382,19 +386,58 @@ def bench_attn_prefill(cases=((32, 8, 2048, 2048), (32, 8, 8192, 8192), (32, 8, 
         cl = torch.tensor([ctx], dtype=torch.int32, device="cuda")
         # causal FLOPs of the last T queries over ctx keys
         fl = 4 * nh * D * (T * ctx - T * (T - 1) / 2)
-        plan = ops.attn_prefill_plan(1, T, ctx, nh, nkv, ksplit=-1)
+        plan = ops.attn_prefill_plan(1, T, ctx, nh, nkv, ksplit=-1, window=WINDOW)
         ws = ops.attn_prefill_workspace(4, T, nh, D, "cuda", 1, nkv, T)
         res = []
         # one throwaway timing first: the first measurement of a shape ran ~7 % slow (clock ramp)
         timeit(lambda: ops.attn_prefill(q, kc, vc, bt, qs, ql, cl, out, T, nh, nkv, D, bs, 1 / math.sqrt(D),
-                                        max_ctx=ctx, ksplit=1, ws=ws), iters=3)
+                                        max_ctx=ctx, ksplit=1, ws=ws, window=WINDOW), iters=3)
         extra = [tuple(int(x) for x in c.split(",")) for c in os.environ.get("PF_SPLITS", "").split(";") if c]
-        for k, km in dict.fromkeys([plan, (1, 1), (2, 8), (2, 16), (4, 4), (4, 8), (4, 16)] + extra):
+        splits = [(1, 1), (2, 8), (2, 16), (4, 4), (4, 8), (4, 16)] + extra
+        if WINDOW:  # the windowed launch has no KV split
+            splits = [(1, 1)]
+        for k, km in dict.fromkeys([plan] + splits):
             us = timeit(lambda: ops.attn_prefill(q, kc, vc, bt, qs, ql, cl, out, T, nh, nkv, D, bs, 1 / math.sqrt(D),
-                                                 max_ctx=ctx, ksplit=k, kmin=km, ws=ws), iters=3)
+                                                 max_ctx=ctx, ksplit=k, kmin=km, ws=ws, window=WINDOW), iters=3)
             tag = "plan" if (k, km) == plan else ""
             res.append(f"{tag}({k},{km if k > 1 else '-'}) {us:7.1f} us {fl / us / 1e6:4.0f} TF/s")
         print(f"attn_prefill nh={nh} nkv={nkv} T={T} ctx={ctx}: " + " | ".join(res), flush=True)
+
+
+def bench_attn_window(W=4096, shape=(32, 8, 128)):
+    """Sliding window against no window on Mistral-7B's attention shape: decode at 4k / 16k / 32k
+    keys in every form the length admits (fused chunks up to 4096 keys, the split grids), and the
+    unsplit prefill of 8192 tokens at 8k / 32k keys in the 8- and 4-wave forms."""
+    nh, nkv, D = shape
+    sc = 1 / math.sqrt(D)
+    for L in (4096, 16384, 32768):
+        kc, vc, bt, sl, q, out = _attn_case(L, nh, nkv, D)
+        forms = [(True, ch, L // ch) for ch in (128, 256) if L <= 4096] + [(False, 128, gc) for gc in (32, 64, 128)]
+        line = []
+        for fused, ch, gc in forms:
+            part, ctr = ops.decode_attn_workspace(1, nh, nkv, D, gc, "cuda", fused=fused)
+            us = [timeit(lambda: ops.attn_decode(q, kc, vc, bt, sl, out, part, ctr, nh, nkv, D, 64, ch, sc,
+                                                 grid_chunks=gc, fused=fused, window=w)) for w in (0, W, 0, W)]
+            line.append(f"{'fused c%d' % ch if fused else 'split g%d' % gc} W=0 {min(us[0], us[2]):6.2f} "
+                        f"W={W} {min(us[1], us[3]):6.2f}")
+        print(f"attn-window nh={nh} nkv={nkv} D={D} L={L:6d} (us): " + "  ".join(line), flush=True)
+    bs, T = 64, 8192
+    for ctx in (8192, 32768):
+        nb = (ctx + bs - 1) // bs + 1
+        kc = torch.randn(nb, nkv, bs, D, device="cuda").to(BF)
+        vc = torch.randn_like(kc)
+        bt = torch.arange(nb, dtype=torch.int32, device="cuda").view(1, -1)
+        q = torch.randn(T, nh * D, device="cuda").to(BF)
+        out = torch.empty_like(q)
+        qs = torch.tensor([0], dtype=torch.int32, device="cuda")
+        ql = torch.tensor([T], dtype=torch.int32, device="cuda")
+        cl = torch.tensor([ctx], dtype=torch.int32, device="cuda")
+        line = []
+        for form in (0, 2):
+            us = [timeit(lambda: ops.attn_prefill(q, kc, vc, bt, qs, ql, cl, out, T, nh, nkv, D, bs, sc, max_ctx=ctx,
+                                                  ksplit=1, form=form, window=w), iters=3) for w in (0, 0, W, W)]
+            line.append(f"form {form} W=0 {min(us[:2]):7.1f} W={W} {min(us[2:]):7.1f}")
+        print(f"attn-prefill-window nh={nh} nkv={nkv} T={T} ctx={ctx} (us): " + "  ".join(line), flush=True)
 
 
 def bench_moe(tokens=(2048, 8192, 16384)):
@@ -456,7 +499,12 @@ def bench_attn_rows_policy(rows=(1, 2, 4, 8, 16, 32), lens=(700, 2560, 8192, 135
 
 
 if __name__ == "__main__":
-    what = sys.argv[1] if len(sys.argv) > 1 else "all"
+    argv = sys.argv[1:]
+    if "--window" in argv:
+        i = argv.index("--window")
+        WINDOW = int(argv[i + 1])
+        del argv[i:i + 2]
+    what = argv[0] if argv else "all"
     if what in ("launch", "all"):
         bench_launch()
     if what in ("attn", "all"):
@@ -494,5 +542,7 @@ if __name__ == "__main__":
         bench_moe()
     if what in ("attn-prefill",):
         bench_attn_prefill()
+    if what in ("attn-window",):  # sliding window (default 4096) vs none, decode and prefill
+        bench_attn_window(WINDOW or 4096)
     if what in ("prefill",):
         bench_prefill()
