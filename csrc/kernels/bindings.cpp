@@ -22,6 +22,12 @@ int llmc_embedding(const void*, const void*, void*, int, int, int, hipStream_t);
 int llmc_lane_exchange_check(const void*, void*, int, hipStream_t);
 int llmc_silu_mul_interleaved(const void*, void*, int, int, hipStream_t);
 int llmc_gemv(int, const void*, int, const void*, float, const void*, void*, int, int, int, int, int, hipStream_t);
+int llmc_gemv_p13(int, const void*, int, const void*, float, const void*, const void*, const void*, void*, int, int, int,
+                  int, hipStream_t);
+int llmc_gemv_qkv_rope_p13(int, const void*, int, const void*, float, const void*, const void*, const void*, int, int,
+                           void*, int, void*, void*, const void*, const void*, const void*, const void*, int, int, int,
+                           int, hipStream_t);
+int llmc_wpack13(const void*, void*, void*, void*, int, int, hipStream_t);
 int llmc_gemvm(int, const void*, int, const void*, float, const void*, void*, int, int, int, int, int, hipStream_t);
 int llmc_moe_gemvm(int, const void*, int, const void*, float, const void*, const void*, int, int, void*, int, int, int,
                    int, hipStream_t);
@@ -125,6 +131,20 @@ PYBIND11_MODULE(_llmc_hip, m) {
   m.def("gemv", [](int M, ptr x, int xs, ptr nw, float eps, ptr W, ptr out, int os, int N, int K, int epi, int mfma,
                    ptr s) {
     check(llmc_gemv(M, P(x), xs, P(nw), eps, P(W), P(out), os, N, K, epi, mfma, S(s)), "gemv");
+  });
+  m.def("gemv_p13", [](int M, ptr x, int xs, ptr nw, float eps, ptr W, ptr planes, ptr hdr, ptr out, int os, int N,
+                       int K, int epi, ptr s) {
+    check(llmc_gemv_p13(M, P(x), xs, P(nw), eps, P(W), P(planes), P(hdr), P(out), os, N, K, epi, S(s)), "gemv_p13");
+  });
+  m.def("gemv_qkv_rope_p13", [](int M, ptr x, int xs, ptr nw, float eps, ptr W, ptr planes, ptr hdr, int N, int K,
+                                ptr qo, int qos, ptr kc, ptr vc, ptr pos, ptr slots, ptr cos_t, ptr sin_t, int nh,
+                                int nkv, int D, int bs, ptr s) {
+    check(llmc_gemv_qkv_rope_p13(M, P(x), xs, P(nw), eps, P(W), P(planes), P(hdr), N, K, P(qo), qos, P(kc), P(vc),
+                                 P(pos), P(slots), P(cos_t), P(sin_t), nh, nkv, D, bs, S(s)),
+          "gemv_qkv_rope_p13");
+  });
+  m.def("wpack13", [](ptr W, ptr planes, ptr hdr, ptr raw_count, int N, int K, ptr s) {
+    check(llmc_wpack13(P(W), P(planes), P(hdr), P(raw_count), N, K, S(s)), "wpack13");
   });
   m.def("moe_gemvm", [](int P, ptr x, int xs, ptr nw, float eps, ptr W, ptr ids, int x_div, int E, ptr out, int os,
                         int N, int K, int epi, ptr s) {

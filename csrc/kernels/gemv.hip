@@ -13,11 +13,40 @@
 
 namespace llmc {
 
+// The 13-bit packed twin of W (gemv_core.h WF_P13), or null planes: the bf16 stream. It rides
+// through the launchers as data, so the packed launch picks its geometry by the same code, hence
+// the same blocks and summation order, as the bf16 launch of the same (M, N, K, epilogue).
+template <int M, int NT, int RPW, int PRO, int EPI, int UNROLL>
+static int launch_gemv_p13(const void* x, int x_stride, const void* nw, float eps, const void* W, const PackedW& pw,
+                           void* out, int out_stride, int N, int K, const RopeEpi& rope, hipStream_t s) {
+  if constexpr (M <= 2 && UNROLL % 4 == 0) {
+    constexpr int WAVES = NT / kWave;
+    auto kern = gemv_p13_kernel<M, NT, RPW, UNROLL, PRO, EPI>;
+    const size_t lds = static_cast<size_t>(M) * K * sizeof(bf16_t) + 2 * M * WAVES * sizeof(float);
+    if (lds > 160 * 1024) return -2;
+    static bool attr_set = false;
+    if (lds > 64 * 1024 && !attr_set) {
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                160 * 1024);
+      attr_set = true;
+    }
+    const int rows_per_block = WAVES * RPW;
+    const int grid = (N + rows_per_block - 1) / rows_per_block;
+    kern<<<grid, NT, lds, s>>>((const bf16_t*)x, x_stride, (const bf16_t*)nw, eps, (const bf16_t*)W, pw, out,
+                               out_stride, N, K, rope);
+    return static_cast<int>(hipGetLastError());
+  } else {
+    return -8;
+  }
+}
+
 template <int M, int NT, int RPW, int PRO, int EPI, int UNROLL_OVERRIDE = 0>
 static int launch_gemv_g(const void* x, int x_stride, const void* nw, float eps, const void* W, void* out,
-                         int out_stride, int N, int K, const RopeEpi& rope, hipStream_t s) {
+                         int out_stride, int N, int K, const RopeEpi& rope, const PackedW& pw, hipStream_t s) {
   constexpr int UNROLL = UNROLL_OVERRIDE ? UNROLL_OVERRIDE : (RPW == 1 ? 4 : (RPW == 2 ? 4 : (M <= 2 ? 4 : 2)));
   constexpr int WAVES = NT / kWave;
+  if (pw.planes != nullptr)
+    return launch_gemv_p13<M, NT, RPW, PRO, EPI, UNROLL>(x, x_stride, nw, eps, W, pw, out, out_stride, N, K, rope, s);
   auto kern = gemv_kernel<M, NT, RPW, UNROLL, PRO, EPI, false>;
   // x [M][K] bf16 | norm partials [M][WAVES] f32 | pair exchange [WAVES/2][M] f32
   const size_t lds = static_cast<size_t>(M) * K * sizeof(bf16_t) + 2 * M * WAVES * sizeof(float);
@@ -67,7 +96,7 @@ static int pick_waves(int N, bool paired) {
 
 template <int M, int PRO, int EPI>
 static int launch_gemv(const void* x, int x_stride, const void* nw, float eps, const void* W, void* out,
-                       int out_stride, int N, int K, const RopeEpi& rope, hipStream_t s) {
+                       int out_stride, int N, int K, const RopeEpi& rope, const PackedW& pw, hipStream_t s) {
   constexpr bool paired = EPI == EPI_SILU || EPI == EPI_ROPE;
   const int w = pick_waves(N, paired);
   // long rows on few blocks (a 70B TP=4 rank's qkv: 2560 x 8192 = 160 fat blocks): 8 loads per
@@ -80,47 +109,48 @@ static int launch_gemv(const void* x, int x_stride, const void* nw, float eps, c
     // blocks of 12 waves x 2 rows
     static const bool rope_rpw1 = std::getenv("LLMC_GEMV_ROPE_RPW1") != nullptr;  // A/B runs only
     if (EPI == EPI_ROPE && w == 12 && N % (2 * 12 * 256) == 0 && !rope_rpw1)
-      return launch_gemv_g<M, 768, 2, PRO, EPI, 4>(x, x_stride, nw, eps, W, out, out_stride, N, K, rope, s);
+      return launch_gemv_g<M, 768, 2, PRO, EPI, 4>(x, x_stride, nw, eps, W, out, out_stride, N, K, rope, pw, s);
     // ... and the SiLU gate/up pairs, at the widest block that still fills whole rounds with two rows
     // per wave (8B gate_up 28672 rows: 14 waves, 1024 blocks; Phi-3 16384: 16 waves, 512)
     static const bool silu_rpw1 = std::getenv("LLMC_GEMV_SILU_RPW1") != nullptr;  // A/B runs only
     if (EPI == EPI_SILU && !silu_rpw1 && K < 8192) {
       if (N % (2 * 16 * 256) == 0)
-        return launch_gemv_g<M, 1024, 2, PRO, EPI, 4>(x, x_stride, nw, eps, W, out, out_stride, N, K, rope, s);
+        return launch_gemv_g<M, 1024, 2, PRO, EPI, 4>(x, x_stride, nw, eps, W, out, out_stride, N, K, rope, pw, s);
       if (N % (2 * 14 * 256) == 0)
-        return launch_gemv_g<M, 896, 2, PRO, EPI, 4>(x, x_stride, nw, eps, W, out, out_stride, N, K, rope, s);
+        return launch_gemv_g<M, 896, 2, PRO, EPI, 4>(x, x_stride, nw, eps, W, out, out_stride, N, K, rope, pw, s);
     }
     if (w == 16 && K >= 8192 && N <= 4096)
-      return launch_gemv_g<M, 1024, 1, PRO, EPI, 8>(x, x_stride, nw, eps, W, out, out_stride, N, K, rope, s);
+      return launch_gemv_g<M, 1024, 1, PRO, EPI, 8>(x, x_stride, nw, eps, W, out, out_stride, N, K, rope, pw, s);
     if (w == 10 && K >= 8192)
-      return launch_gemv_g<M, 640, 1, PRO, EPI, 8>(x, x_stride, nw, eps, W, out, out_stride, N, K, rope, s);
+      return launch_gemv_g<M, 640, 1, PRO, EPI, 8>(x, x_stride, nw, eps, W, out, out_stride, N, K, rope, pw, s);
   }
   switch (w) {
-    case 16: return launch_gemv_g<M, 1024, 1, PRO, EPI>(x, x_stride, nw, eps, W, out, out_stride, N, K, rope, s);
-    case 14: return launch_gemv_g<M, 896, 1, PRO, EPI>(x, x_stride, nw, eps, W, out, out_stride, N, K, rope, s);
-    case 12: return launch_gemv_g<M, 768, 1, PRO, EPI>(x, x_stride, nw, eps, W, out, out_stride, N, K, rope, s);
-    case 10: return launch_gemv_g<M, 640, 1, PRO, EPI>(x, x_stride, nw, eps, W, out, out_stride, N, K, rope, s);
-    case 8: return launch_gemv_g<M, 512, 1, PRO, EPI>(x, x_stride, nw, eps, W, out, out_stride, N, K, rope, s);
-    case 4: return launch_gemv_g<M, 256, 1, PRO, EPI, 8>(x, x_stride, nw, eps, W, out, out_stride, N, K, rope, s);
+    case 16: return launch_gemv_g<M, 1024, 1, PRO, EPI>(x, x_stride, nw, eps, W, out, out_stride, N, K, rope, pw, s);
+    case 14: return launch_gemv_g<M, 896, 1, PRO, EPI>(x, x_stride, nw, eps, W, out, out_stride, N, K, rope, pw, s);
+    case 12: return launch_gemv_g<M, 768, 1, PRO, EPI>(x, x_stride, nw, eps, W, out, out_stride, N, K, rope, pw, s);
+    case 10: return launch_gemv_g<M, 640, 1, PRO, EPI>(x, x_stride, nw, eps, W, out, out_stride, N, K, rope, pw, s);
+    case 8: return launch_gemv_g<M, 512, 1, PRO, EPI>(x, x_stride, nw, eps, W, out, out_stride, N, K, rope, pw, s);
+    case 4: return launch_gemv_g<M, 256, 1, PRO, EPI, 8>(x, x_stride, nw, eps, W, out, out_stride, N, K, rope, pw, s);
     default:  // paired rows that do not tile by 16-32 rows: pairs inside one wave
-      return launch_gemv_g<M, 256, 2, PRO, EPI>(x, x_stride, nw, eps, W, out, out_stride, N, K, rope, s);
+      return launch_gemv_g<M, 256, 2, PRO, EPI>(x, x_stride, nw, eps, W, out, out_stride, N, K, rope, pw, s);
   }
 }
 
 template <int PRO, int EPI>
 static int dispatch_m(int M, const void* x, int x_stride, const void* nw, float eps, const void* W, void* out,
-                      int out_stride, int N, int K, const RopeEpi& rope, hipStream_t s) {
+                      int out_stride, int N, int K, const RopeEpi& rope, const PackedW& pw, hipStream_t s) {
   switch (M) {
-    case 1: return launch_gemv<1, PRO, EPI>(x, x_stride, nw, eps, W, out, out_stride, N, K, rope, s);
-    case 2: return launch_gemv<2, PRO, EPI>(x, x_stride, nw, eps, W, out, out_stride, N, K, rope, s);
-    case 3: return launch_gemv<3, PRO, EPI>(x, x_stride, nw, eps, W, out, out_stride, N, K, rope, s);
-    case 4: return launch_gemv<4, PRO, EPI>(x, x_stride, nw, eps, W, out, out_stride, N, K, rope, s);
+    case 1: return launch_gemv<1, PRO, EPI>(x, x_stride, nw, eps, W, out, out_stride, N, K, rope, pw, s);
+    case 2: return launch_gemv<2, PRO, EPI>(x, x_stride, nw, eps, W, out, out_stride, N, K, rope, pw, s);
+    case 3: return launch_gemv<3, PRO, EPI>(x, x_stride, nw, eps, W, out, out_stride, N, K, rope, pw, s);
+    case 4: return launch_gemv<4, PRO, EPI>(x, x_stride, nw, eps, W, out, out_stride, N, K, rope, pw, s);
     default: return -3;
   }
 }
 
 static int gemv_dispatch(int M, const void* x, int x_stride, const void* norm_w, float eps, const void* W, void* out,
-                         int out_stride, int N, int K, int epi, const RopeEpi& rope, bool mfma, hipStream_t s) {
+                         int out_stride, int N, int K, int epi, const RopeEpi& rope, const PackedW& pw, bool mfma,
+                         hipStream_t s) {
   if (K % 8 != 0) return -1;
   if ((epi == EPI_SILU || epi == EPI_ROPE) && (N % 2 != 0)) return -1;
   // 3-16 rows: the MFMA form (profiles/r2_batched_decode.md: from 3 rows on the VALU dot products,
@@ -132,8 +162,8 @@ static int gemv_dispatch(int M, const void* x, int x_stride, const void* norm_w,
   const bool norm = norm_w != nullptr;
 #define LLMC_GEMV_CASE(E)                                                                                   \
   case E:                                                                                                   \
-    return norm ? dispatch_m<PRO_NORM, E>(M, x, x_stride, norm_w, eps, W, out, out_stride, N, K, rope, s)   \
-                : dispatch_m<PRO_NONE, E>(M, x, x_stride, norm_w, eps, W, out, out_stride, N, K, rope, s);
+    return norm ? dispatch_m<PRO_NORM, E>(M, x, x_stride, norm_w, eps, W, out, out_stride, N, K, rope, pw, s)   \
+                : dispatch_m<PRO_NONE, E>(M, x, x_stride, norm_w, eps, W, out, out_stride, N, K, rope, pw, s);
   switch (epi) {
     LLMC_GEMV_CASE(EPI_BF16)
     LLMC_GEMV_CASE(EPI_F32)
@@ -141,7 +171,7 @@ static int gemv_dispatch(int M, const void* x, int x_stride, const void* norm_w,
     LLMC_GEMV_CASE(EPI_SILU)
     case EPI_ROPE:
       if (!norm) return -5;
-      return dispatch_m<PRO_NORM, EPI_ROPE>(M, x, x_stride, norm_w, eps, W, out, out_stride, N, K, rope, s);
+      return dispatch_m<PRO_NORM, EPI_ROPE>(M, x, x_stride, norm_w, eps, W, out, out_stride, N, K, rope, pw, s);
     default: return -4;
   }
 #undef LLMC_GEMV_CASE
@@ -155,7 +185,19 @@ extern "C" int llmc_gemv(int M, const void* x, int x_stride, const void* norm_w,
                          int out_stride, int N, int K, int epi, int mfma, hipStream_t s) {
   if (epi == EPI_ROPE) return -5;
   RopeEpi rope{};
-  return gemv_dispatch(M, x, x_stride, norm_w, eps, W, out, out_stride, N, K, epi, rope, mfma != 0, s);
+  return gemv_dispatch(M, x, x_stride, norm_w, eps, W, out, out_stride, N, K, epi, rope, PackedW{}, mfma != 0, s);
+}
+
+// llmc_gemv for M <= 2 with the weights streamed from their 13-bit planes (`planes`, `hdr`: wpack.hip;
+// W: the bf16 tensor, read for raw rows). Same geometry, same bits as llmc_gemv.
+extern "C" int llmc_gemv_p13(int M, const void* x, int x_stride, const void* norm_w, float eps, const void* W,
+                             const void* planes, const void* hdr, void* out, int out_stride, int N, int K, int epi,
+                             hipStream_t s) {
+  if (epi == EPI_ROPE) return -5;
+  if (M < 1 || M > kGemvMaxM || K % kP13UnitElems != 0 || planes == nullptr || hdr == nullptr) return -1;
+  RopeEpi rope{};
+  const PackedW pw{static_cast<const uint8_t*>(planes), static_cast<const uint8_t*>(hdr)};
+  return gemv_dispatch(M, x, x_stride, norm_w, eps, W, out, out_stride, N, K, epi, rope, pw, false, s);
 }
 
 // qkv projection for decode with fused RMSNorm prologue and RoPE + paged-KV-write epilogue.
@@ -166,7 +208,21 @@ extern "C" int llmc_gemv_qkv_rope(int M, const void* x, int x_stride, const void
   if (N != (nh + 2 * nkv) * D || D % 2 != 0) return -1;
   RopeEpi rope{(bf16_t*)q_out, q_stride, (bf16_t*)k_cache, (bf16_t*)v_cache, (const int32_t*)positions,
                (const int32_t*)slots, (const float*)cos_t, (const float*)sin_t, nh, nkv, D, bs};
-  return gemv_dispatch(M, x, x_stride, norm_w, eps, W, nullptr, 0, N, K, EPI_ROPE, rope, mfma != 0, s);
+  return gemv_dispatch(M, x, x_stride, norm_w, eps, W, nullptr, 0, N, K, EPI_ROPE, rope, PackedW{}, mfma != 0, s);
+}
+
+// llmc_gemv_qkv_rope for M <= 2 from the 13-bit planes of W (as llmc_gemv_p13).
+extern "C" int llmc_gemv_qkv_rope_p13(int M, const void* x, int x_stride, const void* norm_w, float eps,
+                                      const void* W, const void* planes, const void* hdr, int N, int K, void* q_out,
+                                      int q_stride, void* k_cache, void* v_cache, const void* positions,
+                                      const void* slots, const void* cos_t, const void* sin_t, int nh, int nkv, int D,
+                                      int bs, hipStream_t s) {
+  if (N != (nh + 2 * nkv) * D || D % 2 != 0) return -1;
+  if (M < 1 || M > kGemvMaxM || K % kP13UnitElems != 0 || planes == nullptr || hdr == nullptr) return -1;
+  RopeEpi rope{(bf16_t*)q_out, q_stride, (bf16_t*)k_cache, (bf16_t*)v_cache, (const int32_t*)positions,
+               (const int32_t*)slots, (const float*)cos_t, (const float*)sin_t, nh, nkv, D, bs};
+  const PackedW pw{static_cast<const uint8_t*>(planes), static_cast<const uint8_t*>(hdr)};
+  return gemv_dispatch(M, x, x_stride, norm_w, eps, W, nullptr, 0, N, K, EPI_ROPE, rope, pw, false, s);
 }
 
 // Row-parallel decode projection with the all-reduce fused into the epilogue (EPI_AR, gemv_core.h):

@@ -61,6 +61,38 @@ struct RopeEpi {
   uint32_t gtag;
 };
 
+// Weight formats of the VALU GEMV. WF_P13: the lossless 13-bit planes of wpack.hip (layout there)
+// beside the bf16 tensor. One wave unit = 4 chunks per lane = kP13UnitElems weights in
+// kP13UnitBytes; a row whose header byte is kP13Raw is read from the bf16 tensor instead. The
+// decoded chunks enter the same dot8_bf16 chain in the same order as the bf16 loop's, so for the
+// same geometry the output bits are the bf16 kernel's.
+enum { WF_BF16 = 0, WF_P13 = 1 };
+constexpr int kP13UnitElems = 2048, kP13UnitBytes = 3328, kP13Raw = 0xff;
+struct PackedW {
+  const uint8_t* planes;  // [N][K / 2048][3328]
+  const uint8_t* hdr;     // [N] (readable up to the next multiple of 4)
+};
+struct P13Unit {  // one lane's share of a wave unit: 13 dwords for 32 weights
+  u32x4 l0, l1, n;
+  uint32_t s;
+};
+// chunk C (0..3) of a lane unit -> its 8 bf16 as the bf16 tensor's 16-B chunk
+template <int C>
+__device__ __forceinline__ u32x4 p13_chunk(const P13Unit& p, uint32_t base4) {
+  const uint32_t n = p.n[C];
+  const uint32_t e0 = (n & 0x0f0f0f0fu) + base4, e1 = ((n >> 4) & 0x0f0f0f0fu) + base4;
+  const u32x4& L = C < 2 ? p.l0 : p.l1;
+  const uint32_t lw0 = L[(2 * C) & 3], lw1 = L[(2 * C + 1) & 3];
+  const uint32_t h0 = ((p.s << (7 - 2 * C)) & 0x80808080u) | e0;
+  const uint32_t h1 = ((p.s << (6 - 2 * C)) & 0x80808080u) | e1;
+  u32x4 w;
+  w[0] = __builtin_amdgcn_perm(h0, lw0, 0x05010400u);
+  w[1] = __builtin_amdgcn_perm(h0, lw0, 0x07030602u);
+  w[2] = __builtin_amdgcn_perm(h1, lw1, 0x05010400u);
+  w[3] = __builtin_amdgcn_perm(h1, lw1, 0x07030602u);
+  return w;
+}
+
 // Batched decode (3 <= M <= 32 rows): the MFMA form in gemv_mfma.hip, same prologue/epilogues
 // (one 16-token MFMA column group up to 16 rows, two above). This kernel serves M <= kGemvMaxM
 // (and M <= 4 when K is not a multiple of 128). MoE pairs stay within one token group.
@@ -70,13 +102,16 @@ int gemvm_dispatch(int M, const void* x, int x_stride, const void* norm_w, float
 
 // One block of the GEMV (block (bx, by) of its grid; smem = the block's dynamic LDS): the body of
 // gemv_kernel, also the projection role of fused launches (qkv_attn.hip).
-template <int M, int NT, int RPW, int UNROLL, int PRO, int EPI, bool EXPERT = false>
+template <int M, int NT, int RPW, int UNROLL, int PRO, int EPI, bool EXPERT = false, int WF = WF_BF16>
 __device__ __forceinline__ void gemv_block(const int bx, const int by, char* smem, const bf16_t* __restrict__ x,
                                            int x_stride, const bf16_t* __restrict__ norm_w, float eps,
                                            const bf16_t* __restrict__ W, void* __restrict__ out, int out_stride, int N,
                                            int K, const int32_t* __restrict__ expert_ids, int x_div, const RopeEpi& rope,
-                                           const CarArgs& ar) {
+                                           const CarArgs& ar, const PackedW& pw = PackedW{}) {
   constexpr int WAVES = NT / kWave;
+  constexpr bool P13 = WF == WF_P13;
+  static_assert(!P13 || (!EXPERT && EPI != EPI_AR && EPI != EPI_COMBINE && UNROLL % 4 == 0 && M <= 2),
+                "packed weights: the dense one- and two-row decode forms");
   constexpr bool PAIR_LDS = (EPI == EPI_SILU || EPI == EPI_ROPE) && RPW == 1;  // host: N % (2 * WAVES) == 0
   // RoPE operands through the scalar cache, early (below): one pair per wave (PAIR_LDS: the even
   // wave's row and its partner; RPW == 2: the wave's own two rows)
@@ -154,8 +189,43 @@ __device__ __forceinline__ void gemv_block(const int bx, const int by, char* sme
       }
     }
   }
+  // WF_P13: UB wave units per batch, one batch ahead like the bf16 loop. Units are wave-wide, so
+  // the tail (K is a whole number of units, the last batch maybe not) is masked wave-uniformly.
+  constexpr int UB = P13 ? UNROLL / 4 : 1;
+  const int units = K / kP13UnitElems;
+  P13Unit cur13[P13 ? RPW : 1][UB];
+  const uint8_t* prow[RPW];
+  uint32_t hdr_w[RPW];
+  auto issue13 = [&](P13Unit (&dst)[P13 ? RPW : 1][UB], int ubase) {
+#pragma unroll
+    for (int j = 0; j < UB; ++j) {
+      const int u = min(ubase + j, units - 1);  // clamped tail: loads stay batched
+#pragma unroll
+      for (int r = 0; r < (P13 ? RPW : 1); ++r) {
+        const uint8_t* p = prow[r] + static_cast<int64_t>(u) * kP13UnitBytes + lane * 16;
+        dst[r][j].l0 = load16<true>(p);
+        dst[r][j].l1 = load16<true>(p + 1024);
+        dst[r][j].n = load16<true>(p + 2048);
+        // signs: 4 B per lane at unit + 3072 + 4 lane (p already holds 16 lane)
+        dst[r][j].s = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(p + 3072 - lane * 12));
+      }
+    }
+  };
   __builtin_amdgcn_sched_barrier(0);
-  issue(cur, lane);
+  if constexpr (P13) {
+    // the row headers through the scalar cache (needed only when the first batch is consumed);
+    // the first packed batch goes out whatever they say: a raw row's planes are valid memory
+    const int w_u = __builtin_amdgcn_readfirstlane(wave);
+#pragma unroll
+    for (int r = 0; r < RPW; ++r) {
+      const int n_u = min((bx * WAVES + w_u) * RPW + r, N - 1);
+      hdr_w[r] = ld_scalar(reinterpret_cast<const uint32_t*>(pw.hdr + (n_u & ~3))) >> ((n_u & 3) * 8) & 0xffu;
+      prow[r] = pw.planes + static_cast<int64_t>(n_u) * units * kP13UnitBytes;
+    }
+    issue13(cur13, 0);
+  } else {
+    issue(cur, lane);
+  }
   __builtin_amdgcn_sched_barrier(0);
 
 
@@ -343,21 +413,80 @@ __device__ __forceinline__ void gemv_block(const int bx, const int by, char* sme
   };
   using Full = std::integral_constant<bool, false>;
   using Masked = std::integral_constant<bool, true>;
-  const int full = nchunk / STEP;  // batches in which every lane's chunks are all in range
-  int c0 = lane;
-  for (int it = 0; it + 1 < iters; ++it, c0 += STEP) {  // it < iters - 1 <= full
-    u32x4 nxt[RPW][UNROLL];
-    issue(nxt, c0 + STEP);
-    consume(cur, c0, Full{});
+  auto stream_bf16 = [&]() {
+    const int full = nchunk / STEP;  // batches in which every lane's chunks are all in range
+    int c0 = lane;
+    for (int it = 0; it + 1 < iters; ++it, c0 += STEP) {  // it < iters - 1 <= full
+      u32x4 nxt[RPW][UNROLL];
+      issue(nxt, c0 + STEP);
+      consume(cur, c0, Full{});
 #pragma unroll
-    for (int u = 0; u < UNROLL; ++u)
+      for (int u = 0; u < UNROLL; ++u)
 #pragma unroll
-      for (int r = 0; r < RPW; ++r) cur[r][u] = nxt[r][u];
-  }
-  if (full == iters) {
-    consume(cur, c0, Full{});
+        for (int r = 0; r < RPW; ++r) cur[r][u] = nxt[r][u];
+    }
+    if (full == iters) {
+      consume(cur, c0, Full{});
+    } else {
+      consume(cur, c0, Masked{});
+    }
+  };
+  if constexpr (P13) {
+    bool raw = false;
+    uint32_t base4[RPW];
+#pragma unroll
+    for (int r = 0; r < RPW; ++r) {
+      raw |= hdr_w[r] == kP13Raw;
+      base4[r] = hdr_w[r] * 0x01010101u;
+    }
+    if (raw) {  // wave-uniform: a raw row (or its RPW partner) streams the bf16 tensor
+      issue(cur, lane);
+      stream_bf16();
+    } else {
+      // chunk c of unit u is the bf16 loop's chunk lane + 64 (4 u + c): same x chunk, same order
+      auto consume13 = [&](const P13Unit (&wv)[RPW][UB], int ubase, auto masked) {
+#pragma unroll
+        for (int j = 0; j < UB; ++j) {
+          if (!decltype(masked)::value || ubase + j < units) {
+            const int cb = lane + kWave * 4 * (ubase + j);
+            auto chunk = [&](auto cc) {
+              constexpr int C = decltype(cc)::value;
+              u32x4 w[RPW];
+#pragma unroll
+              for (int r = 0; r < RPW; ++r) w[r] = p13_chunk<C>(wv[r][j], base4[r]);
+#pragma unroll
+              for (int m = 0; m < M; ++m) {
+                const u32x4 xx = xv[m * nchunk + cb + C * kWave];
+#pragma unroll
+                for (int r = 0; r < RPW; ++r) acc[r][m] = dot8_bf16(w[r], xx, acc[r][m]);
+              }
+            };
+            chunk(std::integral_constant<int, 0>{});
+            chunk(std::integral_constant<int, 1>{});
+            chunk(std::integral_constant<int, 2>{});
+            chunk(std::integral_constant<int, 3>{});
+          }
+        }
+      };
+      const int it13 = (units + UB - 1) / UB;
+      int u0 = 0;
+      for (int it = 0; it + 1 < it13; ++it, u0 += UB) {
+        P13Unit nxt[RPW][UB];
+        issue13(nxt, u0 + UB);
+        consume13(cur13, u0, Full{});
+#pragma unroll
+        for (int j = 0; j < UB; ++j)
+#pragma unroll
+          for (int r = 0; r < RPW; ++r) cur13[r][j] = nxt[r][j];
+      }
+      if (units % UB == 0) {
+        consume13(cur13, u0, Full{});
+      } else {
+        consume13(cur13, u0, Masked{});
+      }
+    }
   } else {
-    consume(cur, c0, Masked{});
+    stream_bf16();
   }
 
 #pragma unroll
@@ -538,6 +667,19 @@ __global__ __launch_bounds__(NT) void gemv_kernel(const bf16_t* __restrict__ x, 
   extern __shared__ __attribute__((aligned(16))) char smem[];
   gemv_block<M, NT, RPW, UNROLL, PRO, EPI, EXPERT>(blockIdx.x, blockIdx.y, smem, x, x_stride, norm_w, eps, W, out,
                                                    out_stride, N, K, expert_ids, x_div, rope, ar);
+}
+
+
+// WF_P13 form of gemv_kernel (dense, M <= 2): W stays the bf16 tensor (raw rows), pw its planes
+template <int M, int NT, int RPW, int UNROLL, int PRO, int EPI>
+__global__ __launch_bounds__(NT) void gemv_p13_kernel(const bf16_t* __restrict__ x, int x_stride,
+                                                      const bf16_t* __restrict__ norm_w, float eps,
+                                                      const bf16_t* __restrict__ W, PackedW pw,
+                                                      void* __restrict__ out, int out_stride, int N, int K,
+                                                      RopeEpi rope) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  gemv_block<M, NT, RPW, UNROLL, PRO, EPI, false, WF_P13>(blockIdx.x, blockIdx.y, smem, x, x_stride, norm_w, eps, W,
+                                                          out, out_stride, N, K, nullptr, 1, rope, CarArgs{}, pw);
 }
 
 }  // namespace llmc

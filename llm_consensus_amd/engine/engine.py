@@ -20,6 +20,7 @@ SURVEY.md §7.4).
 from __future__ import annotations
 
 import dataclasses
+import logging
 import math
 import os
 import time
@@ -33,6 +34,7 @@ from ..models.config import ModelConfig, rope_inv_freq
 from ..models.transformer import TransformerWeights
 from ..ops import EPI_BF16, EPI_F32, EPI_RESADD, EPI_SILU, oracle
 from ..parallel.comm import TPGroup
+from ..parallel.placement import packed_weights_mode
 from ..utils import trace
 from ..utils.native import runtime
 
@@ -92,9 +94,17 @@ class EngineConfig:
     # engine whose GPUs also run other engines' decode at the same time (bench.py's N=2 third
     # responder) keeps the separate, 64-block all-reduce launch
     fused_ar: bool = True
+    # decode GEMVs of 1-2 rows stream a lossless 13-bit packed twin of their weights (ops.wpack:
+    # 0.8125 of the bytes, the same output bits) built beside the bf16 tensors at engine build.
+    # "auto": dense models at TP = 1 on the GPU with max_batch <= 2, when the twin fits in the free
+    # device memory with PACKED_MARGIN_BYTES to spare; "on": the same without the memory check;
+    # "off". Environment default (A/B runs): LLMC_PACKED_WEIGHTS.
+    packed_weights: str = dataclasses.field(default_factory=packed_weights_mode)
 
 
 FUSED_CHUNK_SMALL, FUSED_CHUNK_LARGE = 128, 256
+PACKED_MARGIN_BYTES = 4 << 30  # free device memory "auto" leaves after building the packed twins
+log = logging.getLogger(__name__)
 # one-launch qkv + attention by default only for qkv outputs under this many rows (TP shards)
 QKV_ATTN_MAX_ROWS = 2048
 # batching engines: minimum keys per split block (see attn_buckets) when rows x kv heads fill the
@@ -275,6 +285,8 @@ class Engine:
         cos_t, sin_t = oracle.rope_tables(rope_inv_freq(cfg), e.max_context + e.steps_per_graph + 2)
         self.cos_t, self.sin_t = cos_t.to(dev), sin_t.to(dev)
         self._alloc_decode_buffers()
+        with self._on_stream():
+            self._build_packed_weights()
         self._graphs: Dict[int, "torch.cuda.CUDAGraph"] = {}
         self._next_sid = 0
 
@@ -285,6 +297,41 @@ class Engine:
         import contextlib
 
         return contextlib.nullcontext()
+
+    def _build_packed_weights(self) -> None:
+        """The packed decode twins of the weights (``EngineConfig.packed_weights``), with a log line
+        either way. The o_proj twin is skipped where every bucket runs the fused attention + o_proj
+        launch, which reads the bf16 ``w_o``."""
+        mode = str(self.ecfg.packed_weights).lower()
+        self.packed = False
+        if mode not in ("auto", "on", "off"):
+            raise EngineError(f"packed_weights: auto, on or off, got {self.ecfg.packed_weights!r}")
+        why = None
+        if mode == "off":
+            why = "switched off"
+        elif not self.on_gpu:
+            why = "not on a GPU"
+        elif self.cfg.is_moe or self.tp.size != 1:
+            why = "dense models at TP = 1 only"
+        elif self.ecfg.max_batch > ops.GEMV_PACKED_MAX_M:
+            why = f"max_batch {self.ecfg.max_batch} decodes on the MFMA form"
+        if why is None and self.w.p_lm_head is None and not any(L.p_qkv or L.p_gu or L.p_down for L in self.w.layers):
+            with_o = not (self.ecfg.max_batch == 1 and all(self.ao_chunks))
+            need = self.w.packed_demand(with_o)
+            free = torch.cuda.mem_get_info(self.device)[0]
+            if need == 0:
+                why = "no weight with K a multiple of 2048"
+            elif mode == "auto" and need + PACKED_MARGIN_BYTES > free:
+                why = f"the twin ({need / 2**30:.2f} GiB) does not fit in {free / 2**30:.2f} GiB free"
+            else:
+                st = self.w.pack_decode_weights(with_o)
+                log.info("%s: packed weights on: %d of %d tensors, %.2f GiB beside %.2f GiB bf16, raw rows <= %.3f %%",
+                         self.name, st["packed"], st["tensors"], st["bytes"] / 2**30, self.w.nbytes() / 2**30,
+                         100 * st["raw_share"])
+        if why is not None:
+            log.info("%s: packed weights off: %s", self.name, why)
+            return
+        self.packed = True
 
     def _alloc_decode_buffers(self) -> None:
         B, dev, c = self.ecfg.max_batch, self.device, self.cfg
@@ -563,7 +610,7 @@ class Engine:
         accumulate(pbuf[:T])
         self.tp.reduce_scatter_rows(pbuf, hs)
 
-    def _row_parallel(self, x: torch.Tensor, W: torch.Tensor, h: torch.Tensor) -> None:
+    def _row_parallel(self, x: torch.Tensor, W: torch.Tensor, h: torch.Tensor, Wp=None) -> None:
         """h += x @ W^T across the TP group (residual folded into rank 0's partial). Decode rows
         (<= 2, VALU GEMV form) of a group with mapped peers: ONE launch, the all-reduce in the
         GEMV's epilogue (EPI_AR); otherwise the GEMV/GEMM, then the group's all-reduce."""
@@ -571,7 +618,7 @@ class Engine:
         if car is not None and h.is_cuda and x.shape[0] <= 2 and not self.mfma_decode and h.is_contiguous():
             car.gemv_allreduce(x, W, h)
             return
-        ops.linear(x, W, EPI_RESADD if self.tp.rank == 0 else EPI_BF16, out=h, mfma=self.mfma_decode)
+        ops.linear(x, W, EPI_RESADD if self.tp.rank == 0 else EPI_BF16, out=h, mfma=self.mfma_decode, Wp=Wp)
         self.tp.all_reduce_(h)
 
     def _expert_ffn(self, A: torch.Tensor, ids: torch.Tensor, Lw) -> torch.Tensor:
@@ -688,6 +735,7 @@ class Engine:
         qa = self.qa_plan[bi] if B == 1 else None
         dbg = self._debug_layer_io  # eager debug steps only: each layer's input, then the last output
         layers = self.w.layers
+        pk = self.packed  # the 13-bit packed twins where the weights have them (TP = 1, <= 2 rows)
         for li, Lw in enumerate(layers):
             if dbg is not None:
                 dbg.append(h.clone())
@@ -708,7 +756,7 @@ class Engine:
             else:
                 ops.qkv_rope(h, Lw.w_qkv, Lw.ln1, c.rms_eps, q, self.k_cache[li], self.v_cache[li],
                              self.positions[:B], self.slots[:B], self.cos_t, self.sin_t, self.nh, self.nkv, self.D,
-                             self.bs, mfma=self.mfma_decode)
+                             self.bs, mfma=self.mfma_decode, Wp=Lw.p_qkv if pk else None)
                 if ao_chunk:  # one-row engines: attention + o_proj + residual (+ TP all-reduce) in one launch
                     routed = self.ao_router[bi] and h.is_cuda  # ... (+ the MoE router)
                     self._attn_oproj(q, li, Lw, h, attn, ao_chunk, routed)
@@ -716,12 +764,13 @@ class Engine:
                     ops.attn_decode(q, self.k_cache[li], self.v_cache[li], self.block_tables[:B], self.seq_lens[:B],
                                     attn, part[:B], self.attn_counters[:B], self.nh, self.nkv, self.D, self.bs, chunk,
                                     self.scale, grid_chunks, fused=fused, fault=self.attn_fault, window=self.window)
-                    self._row_parallel(attn, Lw.w_o, h)
+                    self._row_parallel(attn, Lw.w_o, h, Lw.p_o if pk else None)
             if c.is_moe:
                 self._moe_decode(h, Lw, B, routed)
             else:
-                ops.linear(h, Lw.w_gu, EPI_SILU, out=act, norm_w=Lw.ln2, eps=c.rms_eps, mfma=self.mfma_decode)
-                self._row_parallel(act, Lw.w_down, h)
+                ops.linear(h, Lw.w_gu, EPI_SILU, out=act, norm_w=Lw.ln2, eps=c.rms_eps, mfma=self.mfma_decode,
+                           Wp=Lw.p_gu if pk else None)
+                self._row_parallel(act, Lw.w_down, h, Lw.p_down if pk else None)
         if dbg is not None:
             dbg.append(h.clone())
         self._lm_head_sample(B)
@@ -778,7 +827,7 @@ class Engine:
     def _lm_head_sample(self, B: int) -> None:
         lg = self.logits_local[:B]
         ops.linear(self.h[:B], self.w.lm_head, EPI_F32, out=lg, norm_w=self.w.final_norm, eps=self.cfg.rms_eps,
-                   mfma=self.mfma_decode)
+                   mfma=self.mfma_decode, Wp=self.w.p_lm_head if self.packed else None)
         logits = self._gather_logits(B)
         self._sample(B, logits)
 

@@ -80,6 +80,18 @@ class ModelConfig:
     def weight_bytes(self, dtype_bytes: int = 2) -> int:
         return self.num_params() * dtype_bytes
 
+    def packed_twin_bytes(self) -> int:
+        """Bytes of the 13-bit packed decode twins (ops.wpack) an unsharded dense engine builds beside
+        its bf16 weights: 13/16 of every decode GEMV weight whose K is a whole number of 2048-weight
+        units (the o_proj twin counted too: the upper bound); 0 for MoE."""
+        if self.is_moe:
+            return 0
+        h, i = self.hidden, self.intermediate
+        shapes = [(self.qkv_size, h), (h, self.q_size), (2 * i, h), (h, i)]
+        per_layer = sum(n * k for n, k in shapes if k % 2048 == 0)
+        head = self.vocab * h if h % 2048 == 0 else 0
+        return (self.n_layers * per_layer + head) * 13 // 8
+
     def kv_bytes_per_token(self, dtype_bytes: int = 2) -> int:
         return 2 * self.n_layers * self.kv_size * dtype_bytes
 

@@ -32,7 +32,10 @@ from .config import ModelConfig
 
 
 class LayerWeights:
-    __slots__ = ("ln1", "ln2", "w_qkv", "w_o", "w_gu", "w_down", "w_router")
+    TENSORS = ("ln1", "ln2", "w_qkv", "w_o", "w_gu", "w_down", "w_router")
+    # p_*: the 13-bit packed twin (ops.wpack.PackedWeight) of w_*, or None: decode streams bf16
+    PACKED = ("p_qkv", "p_o", "p_gu", "p_down")
+    __slots__ = TENSORS + PACKED
 
     def __init__(self):
         for s in self.__slots__:
@@ -68,6 +71,7 @@ class TransformerWeights:
         self.kv_size = self.nkv * cfg.head_dim
         self.qkv_size = self.q_size + 2 * self.kv_size
         self.layers: List[LayerWeights] = []
+        self.p_lm_head = None  # packed twin of lm_head (pack_decode_weights)
         self._build()
         self.source = None  # release the checkpoint's file handles
 
@@ -158,16 +162,59 @@ class TransformerWeights:
         self.final_norm = self.final_norm.to(device)
         self.lm_head = self.lm_head.to(device)
         for L in self.layers:
-            for s in LayerWeights.__slots__:
+            for s in LayerWeights.TENSORS:
                 t = getattr(L, s)
                 if t is not None:
                     setattr(L, s, t.to(device))
         return self
 
+    # -- packed decode twins ---------------------------------------------------------------------
+    def packed_demand(self, with_o: bool = True) -> int:
+        """Bytes ``pack_decode_weights`` would allocate (dense models; tensors off the unit size
+        are not packed and cost nothing)."""
+        from ..ops import wpack
+
+        ts = [self.lm_head]
+        for L in self.layers:
+            ts += [L.w_qkv, L.w_gu, L.w_down] + ([L.w_o] if with_o else [])
+        return sum(wpack.packed_nbytes(*t.shape) for t in ts if t.dim() == 2 and wpack.packable_shape(*t.shape))
+
+    def pack_decode_weights(self, with_o: bool = True) -> dict:
+        """Build the 13-bit packed twins of the decode GEMVs' weights (``ops.wpack``) beside the bf16
+        tensors, which stay (prefill and raw rows read them). A tensor off the unit size, or with
+        more than 1 % raw rows, keeps bf16 only. -> {"tensors", "packed", "bytes", "raw_share"}
+        (the largest share of raw rows among the tensors looked at)."""
+        from ..ops import wpack
+
+        if self.cfg.is_moe:
+            raise ValueError("packed weights: dense models only")
+        st = {"tensors": 0, "packed": 0, "bytes": 0, "raw_share": 0.0}
+
+        def twin(W):
+            st["tensors"] += 1
+            pw, share = wpack.pack_if_worthwhile(W)
+            st["raw_share"] = max(st["raw_share"], share)
+            if pw is not None:
+                st["packed"] += 1
+                st["bytes"] += pw.nbytes()
+            return pw
+
+        self.p_lm_head = twin(self.lm_head)
+        for L in self.layers:
+            L.p_qkv, L.p_gu, L.p_down = twin(L.w_qkv), twin(L.w_gu), twin(L.w_down)
+            L.p_o = twin(L.w_o) if with_o else None
+        return st
+
+    def packed_nbytes(self) -> int:
+        tot = self.p_lm_head.nbytes() if self.p_lm_head is not None else 0
+        for L in self.layers:
+            tot += sum(getattr(L, s).nbytes() for s in LayerWeights.PACKED if getattr(L, s) is not None)
+        return tot
+
     def nbytes(self) -> int:
         tot = self.embed.numel() + self.final_norm.numel() + self.lm_head.numel()
         for L in self.layers:
-            for s in LayerWeights.__slots__:
+            for s in LayerWeights.TENSORS:
                 t = getattr(L, s)
                 if t is not None:
                     tot += t.numel()

@@ -14,10 +14,11 @@ from typing import Optional
 import torch
 
 from ..utils.native import kernels
-from . import oracle
+from . import oracle, wpack
 
 EPI_BF16, EPI_F32, EPI_RESADD, EPI_SILU, EPI_ROPE = 0, 1, 2, 3, 4
 GEMV_MAX_M = 32      # decode rows on the weight-streaming path (VALU GEMV 1-2, MFMA form 3-32)
+GEMV_PACKED_MAX_M = 2  # rows that can stream the 13-bit packed twin of a weight (the VALU GEMV's)
 MOE_GEMVM_MAX_TOKENS = 16  # batched MoE decode: (token, expert) pairs of <= 16 tokens per launch
 MOE_GEMV_MAX_M = 4   # MoE: per-(row, expert) GEMVs up to this many rows, then the grouped GEMM
 
@@ -84,8 +85,14 @@ def silu_mul_interleaved(gu: torch.Tensor, out: Optional[torch.Tensor] = None) -
     return out
 
 
+def _use_packed(Wp, M: int, N: int, K: int, mfma: bool) -> bool:
+    # the packed stream serves the VALU GEMV's rows (1-2) only; everything else reads bf16
+    return Wp is not None and M <= GEMV_PACKED_MAX_M and not mfma and Wp.N == N and Wp.K == K
+
+
 def linear(x: torch.Tensor, W: torch.Tensor, epi: int = EPI_BF16, out: Optional[torch.Tensor] = None,
-           norm_w: Optional[torch.Tensor] = None, eps: float = 1e-5, mfma: bool = False) -> torch.Tensor:
+           norm_w: Optional[torch.Tensor] = None, eps: float = 1e-5, mfma: bool = False,
+           Wp: Optional["wpack.PackedWeight"] = None) -> torch.Tensor:
     """y = (rmsnorm(x)*norm_w if norm_w else x) @ W^T with a fused epilogue.
 
     M <= 32 rows -> weight streaming (decode; the norm runs in its prologue): the VALU GEMV for 1-2
@@ -94,6 +101,8 @@ def linear(x: torch.Tensor, W: torch.Tensor, epi: int = EPI_BF16, out: Optional[
     (csrc/kernels/gemm.hip; a norm is a separate rmsnorm launch first).
     Epilogues: bf16 | f32 | EPI_RESADD (accumulates into ``out`` in place) | EPI_SILU (interleaved
     gate/up columns -> silu(g) * u, [M, N / 2]). One code path per shape class, all hand-written.
+    ``Wp``: the 13-bit packed twin of ``W`` (``ops.wpack``); 1-2 rows then stream it instead of
+    ``W`` (fewer bytes, the same output bits), every other row count reads ``W``.
     """
     if not x.is_cuda:
         return oracle.linear(x, W, epi, out, norm_w, eps)
@@ -108,6 +117,10 @@ def linear(x: torch.Tensor, W: torch.Tensor, epi: int = EPI_BF16, out: Optional[
             raise ValueError("EPI_RESADD needs out")
         n_out = N // 2 if epi == EPI_SILU else N
         out = torch.empty(M, n_out, dtype=torch.float32 if epi == EPI_F32 else torch.bfloat16, device=x.device)
+    if _use_packed(Wp, M, N, K, mfma):
+        kernels().gemv_p13(M, _p(x), x.stride(0), _p(norm_w), float(eps), _p(W), _p(Wp.planes), _p(Wp.hdr), _p(out),
+                           out.stride(0), N, K, epi, _s(x))
+        return out
     if M <= 4 or (M <= GEMV_MAX_M and K % 128 == 0 and x.stride(0) % 8 == 0):
         kernels().gemv(M, _p(x), x.stride(0), _p(norm_w), float(eps), _p(W), _p(out), out.stride(0), N, K, epi,
                        int(mfma), _s(x))
@@ -216,14 +229,19 @@ def rope_kv_write(qkv, positions, cos_t, sin_t, k_cache, v_cache, slots, nh, nkv
 
 
 def qkv_rope(x, W, norm_w, eps, q_out, k_cache, v_cache, positions, slots, cos_t, sin_t, nh, nkv, D, bs,
-             mfma: bool = False) -> None:
-    """Decode qkv projection: fused RMSNorm prologue + RoPE/KV-write epilogue (one launch; form as
-    ``linear``)."""
+             mfma: bool = False, Wp: Optional["wpack.PackedWeight"] = None) -> None:
+    """Decode qkv projection: fused RMSNorm prologue + RoPE/KV-write epilogue (one launch; form and
+    ``Wp`` as ``linear``)."""
     if not x.is_cuda:
         qkv = oracle.linear(x, W, EPI_BF16, None, norm_w, eps)
         oracle.rope_kv_write(qkv, positions, cos_t, sin_t, k_cache, v_cache, slots, nh, nkv, D, bs, q_out)
         return
     M, K = x.shape
+    if _use_packed(Wp, M, W.shape[0], K, mfma):
+        kernels().gemv_qkv_rope_p13(M, _p(x), x.stride(0), _p(norm_w), float(eps), _p(W), _p(Wp.planes), _p(Wp.hdr),
+                                    W.shape[0], K, _p(q_out), q_out.stride(0), _p(k_cache), _p(v_cache),
+                                    _p(positions), _p(slots), _p(cos_t), _p(sin_t), nh, nkv, D, bs, _s(x))
+        return
     if M > 4 and (K % 128 != 0 or x.stride(0) % 8 != 0):  # outside the MFMA decode form: prefill's path
         qkv = linear(x, W, EPI_BF16, norm_w=norm_w, eps=eps)
         rope_kv_write(qkv, positions, cos_t, sin_t, k_cache, v_cache, slots, nh, nkv, D, bs, q_out)

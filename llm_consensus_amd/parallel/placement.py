@@ -21,6 +21,14 @@ HBM_BYTES = 288 * 10**9
 USABLE_FRACTION = 0.92
 
 
+def packed_weights_mode() -> str:
+    """Default of ``EngineConfig.packed_weights``: "auto" (on where it applies and fits), "on" or
+    "off"; LLMC_PACKED_WEIGHTS overrides it (A/B runs). The placement counts the packed twins in an
+    engine's weight demand unless this says "off"."""
+    v = os.environ.get("LLMC_PACKED_WEIGHTS", "auto").strip().lower()
+    return {"1": "on", "true": "on", "0": "off", "false": "off"}.get(v, v if v in ("auto", "on", "off") else "auto")
+
+
 @dataclasses.dataclass
 class ModelDemand:
     name: str

@@ -29,6 +29,7 @@ from typing import Dict, List, Optional
 from ..catalog import PROVIDER_LOCAL, ModelSpec
 from ..context import Context, ContextError
 from ..parallel.placement import (HBM_BYTES, USABLE_FRACTION, ModelDemand, alone_plan, default_gpus, describe,
+                                  packed_weights_mode,
                                   fused_ar_plan, solve)
 from ..utils import trace as tracing
 from ..utils.tokenizer import tokenizer_for
@@ -174,7 +175,11 @@ class LocalBackend:
                 tp = len(pins[s.name])
             else:
                 tp = 1 if force_cpu else min(c.default_tp, len(gpu_ids))
-            demands.append(ModelDemand(s.name, c.weight_bytes(), c.kv_bytes_per_token() * ctx_len, tp, s.name == judge))
+            # an unsharded dense GPU engine also builds the packed decode twins of its weights
+            # (EngineConfig.packed_weights, unless switched off)
+            twin = c.packed_twin_bytes() if (tp == 1 and not force_cpu and packed_weights_mode() != "off") else 0
+            demands.append(ModelDemand(s.name, c.weight_bytes() + twin, c.kv_bytes_per_token() * ctx_len, tp,
+                                       s.name == judge))
         if force_cpu and not pins:
             from ..parallel.placement import Placement
 

@@ -192,6 +192,58 @@ def bench_gemv():
         print(f"gemv N={N:6d} K={K:5d} epi={epi}: {us:8.2f} us  {N * K * 2 / us / 1e6:6.2f} TB/s")
 
 
+def bench_packed(shapes=None, rows=(1,), only=None):
+    """The decode GEMVs on the 13-bit packed weight planes against the bf16 stream, each with its
+    real epilogue, on COLD weights (the graph cycles through copies of W beyond the 256 MB MALL, as
+    bench_gemv_sweep). Bytes: bf16 N K 2, packed N K 13 / 8. ``--only qkv,down``: those shapes;
+    ``--rows2``: two rows as well."""
+    from llm_consensus_amd.ops import wpack
+
+    nh, nkv, D, bs = 32, 8, 128, 64
+    cases = shapes or [("qkv", 6144, 4096, 4, True), ("o", 4096, 4096, 2, False), ("gate_up", 28672, 4096, 3, True),
+                       ("down", 4096, 14336, 2, False), ("lm_head", 128256, 4096, 1, True)]
+    for name, N, K, epi, norm in cases:
+        if only and name not in only:
+            continue
+        copies = max(2, (1 << 30) // (N * K * 2))
+        Ws = [(torch.randn(N, K, device="cuda") * K ** -0.5).to(BF) for _ in range(copies)]
+        Ps = [wpack.pack(W) for W in Ws]
+        nw = torch.ones(K, dtype=BF, device="cuda") if norm else None
+        for M in rows:
+            x = torch.randn(M, K, device="cuda").to(BF)
+            if epi == 4:
+                q = torch.zeros(M, nh * D, dtype=BF, device="cuda")
+                kc = torch.zeros(4, nkv, bs, D, dtype=BF, device="cuda")
+                vc = torch.zeros_like(kc)
+                pos = torch.arange(M, dtype=torch.int32, device="cuda")
+                slots = torch.arange(M, dtype=torch.int32, device="cuda")
+                cos_t = torch.ones(16, D // 2, device="cuda")
+                sin_t = torch.zeros(16, D // 2, device="cuda")
+
+                def run(packed):
+                    for W, P in zip(Ws, Ps):
+                        ops.qkv_rope(x, W, nw, 1e-5, q, kc, vc, pos, slots, cos_t, sin_t, nh, nkv, D, bs,
+                                     Wp=P if packed else None)
+            else:
+                out = torch.zeros(M, N // 2 if epi == 3 else N, dtype=torch.float32 if epi == 1 else BF, device="cuda")
+
+                def run(packed):
+                    for W, P in zip(Ws, Ps):
+                        ops.linear(x, W, epi, out=out, norm_w=nw, Wp=P if packed else None)
+            res = []
+            for _ in range(2):  # alternate the two forms twice: the spread is the noise floor
+                res.append((timeit(lambda: run(False), iters=4, warm=1) / copies,
+                            timeit(lambda: run(True), iters=4, warm=1) / copies))
+            b = min(r[0] for r in res)
+            p = min(r[1] for r in res)
+            gb = N * K * 2 / 1e3
+            print(f"packed {name:8s} N={N:6d} K={K:5d} M={M}: bf16 {b:7.2f} us ({gb / b / 1e3:5.2f} TB/s)  "
+                  f"p13 {p:7.2f} us ({gb * 0.8125 / p / 1e3:5.2f} TB/s)  ratio {p / b:.3f}  "
+                  f"raw rows {sum(P.raw_rows for P in Ps)}/{copies * N}  runs {res}", flush=True)
+        del Ws, Ps
+        torch.cuda.empty_cache()
+
+
 SWEEP = ["256x1u8", "256x2u4", "256x4u4", "512x1u8", "512x2u4", "128x1u8", "64x1u8", "1024x1u4", "256x1u4",
          "256x2u8", "512x4u2", "128x2u4", "1024x1u8", "1024x2u4", "1024x2u2", "1024x1u2", "768x1u4", "1024x4u2", "1024x1u6",
          "768x2u4", "640x1u8", "896x1u4", "768x2u2", "1024x2u2b"]
@@ -517,6 +569,9 @@ if __name__ == "__main__":
         bench_gemv()
     if what in ("sweep",):
         bench_gemv_sweep()
+    if what in ("packed",):
+        bench_packed(rows=(1, 2) if "--rows2" in argv else (1,),
+                     only=argv[argv.index("--only") + 1].split(",") if "--only" in argv else None)
     if what in ("sweep-phi3",):  # Phi-3-mini shapes (K = 3072 / 8192)
         bench_gemv_sweep([(9216, 3072), (16384, 3072), (3072, 3072), (3072, 8192)])
     if what in ("sweep-tp8",):  # one TP=8 rank of Llama-3-8B: qkv, gate_up, o, down
