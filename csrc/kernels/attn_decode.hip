@@ -307,11 +307,22 @@ extern "C" int llmc_attn_decode(const void* q, int q_stride, const void* k_cache
   if (static_cast<int64_t>(max_chunks + max_groups) * G * (D / 4 + 1) * 16 >= (1ll << 31)) return -4;
   dim3 grid(grid_chunks, nkv, B);
   const bool f = fused != 0;
+  // G = 5, 6, 7: Qwen2.5 (40 / 8, 12 / 2, 28 / 4 and 14 / 2 heads). The kernel bodies take any
+  // G <= 16: the MFMA tile's unused head columns are dropped, the merges index (head, quad) by division
+#define LLMC_ATTN_G(GG)                                                                                             \
+  case GG:                                                                                                          \
+    return launch_g<GG>(f, D, grid, s, q, q_stride, k_cache, v_cache, block_tables, bt_stride, seq_lens, part,       \
+                        counters, out, out_stride, nkv, bs, nblocks, chunk, max_chunks, gsize, max_groups, scale,    \
+                        static_cast<int*>(fault), window);
   switch (G) {
-    case 1: return launch_g<1>(f, D, grid, s, q, q_stride, k_cache, v_cache, block_tables, bt_stride, seq_lens, part, counters, out, out_stride, nkv, bs, nblocks, chunk, max_chunks, gsize, max_groups, scale, static_cast<int*>(fault), window);
-    case 2: return launch_g<2>(f, D, grid, s, q, q_stride, k_cache, v_cache, block_tables, bt_stride, seq_lens, part, counters, out, out_stride, nkv, bs, nblocks, chunk, max_chunks, gsize, max_groups, scale, static_cast<int*>(fault), window);
-    case 4: return launch_g<4>(f, D, grid, s, q, q_stride, k_cache, v_cache, block_tables, bt_stride, seq_lens, part, counters, out, out_stride, nkv, bs, nblocks, chunk, max_chunks, gsize, max_groups, scale, static_cast<int*>(fault), window);
-    case 8: return launch_g<8>(f, D, grid, s, q, q_stride, k_cache, v_cache, block_tables, bt_stride, seq_lens, part, counters, out, out_stride, nkv, bs, nblocks, chunk, max_chunks, gsize, max_groups, scale, static_cast<int*>(fault), window);
+    LLMC_ATTN_G(1)
+    LLMC_ATTN_G(2)
+    LLMC_ATTN_G(4)
+    LLMC_ATTN_G(5)
+    LLMC_ATTN_G(6)
+    LLMC_ATTN_G(7)
+    LLMC_ATTN_G(8)
     default: return -3;
   }
+#undef LLMC_ATTN_G
 }

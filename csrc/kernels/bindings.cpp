@@ -26,7 +26,7 @@ int llmc_gemv_p13(int, const void*, int, const void*, float, const void*, const 
                   int, hipStream_t);
 int llmc_gemv_qkv_rope_p13(int, const void*, int, const void*, float, const void*, const void*, const void*, int, int,
                            void*, int, void*, void*, const void*, const void*, const void*, const void*, int, int, int,
-                           int, hipStream_t);
+                           int, const void*, hipStream_t);
 int llmc_wpack13(const void*, void*, void*, void*, int, int, hipStream_t);
 int llmc_gemvm(int, const void*, int, const void*, float, const void*, void*, int, int, int, int, int, hipStream_t);
 int llmc_moe_gemvm(int, const void*, int, const void*, float, const void*, const void*, int, int, void*, int, int, int,
@@ -37,7 +37,7 @@ int llmc_gemm_narrow(const void*, int, const void*, int, void*, int, int, int, i
 int llmc_gemm_kind(const void*, int, const void*, int, void*, int, int, int, int, int, int, hipStream_t);
 int llmc_gemm_plan(int, int);
 int llmc_rope_kv_write(const void*, int, void*, int, const void*, const void*, const void*, void*, void*, const void*,
-                       int, int, int, int, int, hipStream_t);
+                       int, int, int, int, int, const void*, hipStream_t);
 int llmc_attn_decode_groups(int);
 int llmc_qkv_attn_check(int, int, int, int);
 int llmc_qkv_attn(const void*, const void*, float, const void*, int, void*, void*, void*, const void*, const void*,
@@ -53,7 +53,8 @@ int llmc_attn_oproj(const void*, const void*, const void*, const void*, int, con
 int llmc_attn_decode(const void*, int, const void*, const void*, const void*, int, const void*, void*, void*, void*,
                      int, int, int, int, int, int, int, int, int, int, float, int, void*, int, hipStream_t);
 int llmc_gemv_qkv_rope(int, const void*, int, const void*, float, const void*, int, int, void*, int, void*, void*,
-                       const void*, const void*, const void*, const void*, int, int, int, int, int, hipStream_t);
+                       const void*, const void*, const void*, const void*, int, int, int, int, int, const void*,
+                       hipStream_t);
 int llmc_attn_prefill(const void*, int, const void*, const void*, const void*, int, const void*, const void*,
                       const void*, void*, int, int, int, int, int, int, int, float, int, int, void*, void*, int,
                       int, int, hipStream_t);
@@ -138,11 +139,15 @@ PYBIND11_MODULE(_llmc_hip, m) {
   });
   m.def("gemv_qkv_rope_p13", [](int M, ptr x, int xs, ptr nw, float eps, ptr W, ptr planes, ptr hdr, int N, int K,
                                 ptr qo, int qos, ptr kc, ptr vc, ptr pos, ptr slots, ptr cos_t, ptr sin_t, int nh,
-                                int nkv, int D, int bs, ptr s) {
+                                int nkv, int D, int bs, ptr s, ptr bias) {
     check(llmc_gemv_qkv_rope_p13(M, P(x), xs, P(nw), eps, P(W), P(planes), P(hdr), N, K, P(qo), qos, P(kc), P(vc),
-                                 P(pos), P(slots), P(cos_t), P(sin_t), nh, nkv, D, bs, S(s)),
+                                 P(pos), P(slots), P(cos_t), P(sin_t), nh, nkv, D, bs, P(bias), S(s)),
           "gemv_qkv_rope_p13");
-  });
+  }, py::arg("M"), py::arg("x"), py::arg("x_stride"), py::arg("norm_w"), py::arg("eps"), py::arg("W"),
+     py::arg("planes"), py::arg("hdr"), py::arg("N"), py::arg("K"), py::arg("q_out"), py::arg("q_stride"),
+     py::arg("k_cache"), py::arg("v_cache"), py::arg("positions"), py::arg("slots"), py::arg("cos_t"),
+     py::arg("sin_t"), py::arg("nh"), py::arg("nkv"), py::arg("D"), py::arg("bs"), py::arg("stream"),
+     py::arg("bias") = 0);  // bias: bf16 [N] in W's row order, 0 = none
   m.def("wpack13", [](ptr W, ptr planes, ptr hdr, ptr raw_count, int N, int K, ptr s) {
     check(llmc_wpack13(P(W), P(planes), P(hdr), P(raw_count), N, K, S(s)), "wpack13");
   });
@@ -168,11 +173,14 @@ PYBIND11_MODULE(_llmc_hip, m) {
     check(llmc_gemm_narrow(P(A), lda, P(W), ldw, P(C), ldc, M, N, K, epi, S(s)), "gemm_narrow");
   });
   m.def("rope_kv_write", [](ptr qkv, int qs, ptr qo, int qos, ptr pos, ptr cos_t, ptr sin_t, ptr kc, ptr vc,
-                            ptr slots, int T, int nh, int nkv, int D, int bs, ptr s) {
+                            ptr slots, int T, int nh, int nkv, int D, int bs, ptr s, ptr bias) {
     check(llmc_rope_kv_write(P(qkv), qs, P(qo), qos, P(pos), P(cos_t), P(sin_t), P(kc), P(vc), P(slots), T, nh, nkv, D,
-                             bs, S(s)),
+                             bs, P(bias), S(s)),
           "rope_kv_write");
-  });
+  }, py::arg("qkv"), py::arg("qkv_stride"), py::arg("q_out"), py::arg("q_stride"), py::arg("positions"),
+     py::arg("cos_t"), py::arg("sin_t"), py::arg("k_cache"), py::arg("v_cache"), py::arg("slots"), py::arg("T"),
+     py::arg("nh"), py::arg("nkv"), py::arg("D"), py::arg("bs"), py::arg("stream"),
+     py::arg("bias") = 0);  // bias: bf16 [(nh + 2 nkv) D] in the qkv columns' order (16-B aligned), 0 = none
   m.def("attn_decode_groups", [](int max_chunks) { return llmc_attn_decode_groups(max_chunks); });
   m.def("qkv_attn_check", [](int nh, int nkv, int D, int K) { return llmc_qkv_attn_check(nh, nkv, D, K); });
   m.def("qkv_attn", [](ptr x, ptr nw, float eps, ptr W, int K, ptr qo, ptr kc, ptr vc, ptr pos, ptr slots, ptr cos_t,
@@ -221,11 +229,15 @@ PYBIND11_MODULE(_llmc_hip, m) {
      py::arg("fused"), py::arg("fault"), py::arg("stream"), py::arg("window") = 0);
   m.def("gemv_qkv_rope", [](int M, ptr x, int xs, ptr nw, float eps, ptr W, int N, int K, ptr qo, int qos, ptr kc,
                             ptr vc, ptr pos, ptr slots, ptr cos_t, ptr sin_t, int nh, int nkv, int D, int bs,
-                            int mfma, ptr s) {
+                            int mfma, ptr s, ptr bias) {
     check(llmc_gemv_qkv_rope(M, P(x), xs, P(nw), eps, P(W), N, K, P(qo), qos, P(kc), P(vc), P(pos), P(slots),
-                             P(cos_t), P(sin_t), nh, nkv, D, bs, mfma, S(s)),
+                             P(cos_t), P(sin_t), nh, nkv, D, bs, mfma, P(bias), S(s)),
           "gemv_qkv_rope");
-  });
+  }, py::arg("M"), py::arg("x"), py::arg("x_stride"), py::arg("norm_w"), py::arg("eps"), py::arg("W"), py::arg("N"),
+     py::arg("K"), py::arg("q_out"), py::arg("q_stride"), py::arg("k_cache"), py::arg("v_cache"),
+     py::arg("positions"), py::arg("slots"), py::arg("cos_t"), py::arg("sin_t"), py::arg("nh"), py::arg("nkv"),
+     py::arg("D"), py::arg("bs"), py::arg("mfma"), py::arg("stream"),
+     py::arg("bias") = 0);  // bias: bf16 [N] in W's row order, 0 = none
   m.def("attn_prefill", [](ptr q, int qs, ptr kc, ptr vc, ptr bt, int bts, ptr qst, ptr ql, ptr cl, ptr out, int os,
                            int B, int max_qlen, int nh, int nkv, int D, int bs, float scale, int ksplit, int kmin,
                            ptr part, ptr counters, int T, int form, ptr s, int window) {

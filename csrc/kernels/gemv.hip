@@ -201,13 +201,15 @@ extern "C" int llmc_gemv_p13(int M, const void* x, int x_stride, const void* nor
 }
 
 // qkv projection for decode with fused RMSNorm prologue and RoPE + paged-KV-write epilogue.
+// bias (nullable): the projection's bias [N] bf16 in W's row order, added in f32 before the rotation.
 extern "C" int llmc_gemv_qkv_rope(int M, const void* x, int x_stride, const void* norm_w, float eps, const void* W,
                                   int N, int K, void* q_out, int q_stride, void* k_cache, void* v_cache,
                                   const void* positions, const void* slots, const void* cos_t, const void* sin_t,
-                                  int nh, int nkv, int D, int bs, int mfma, hipStream_t s) {
-  if (N != (nh + 2 * nkv) * D || D % 2 != 0) return -1;
+                                  int nh, int nkv, int D, int bs, int mfma, const void* bias, hipStream_t s) {
+  if (N != (nh + 2 * nkv) * D || D % 2 != 0 || reinterpret_cast<uintptr_t>(bias) % 4 != 0) return -1;
   RopeEpi rope{(bf16_t*)q_out, q_stride, (bf16_t*)k_cache, (bf16_t*)v_cache, (const int32_t*)positions,
                (const int32_t*)slots, (const float*)cos_t, (const float*)sin_t, nh, nkv, D, bs};
+  rope.bias = static_cast<const bf16_t*>(bias);
   return gemv_dispatch(M, x, x_stride, norm_w, eps, W, nullptr, 0, N, K, EPI_ROPE, rope, PackedW{}, mfma != 0, s);
 }
 
@@ -216,11 +218,12 @@ extern "C" int llmc_gemv_qkv_rope_p13(int M, const void* x, int x_stride, const 
                                       const void* W, const void* planes, const void* hdr, int N, int K, void* q_out,
                                       int q_stride, void* k_cache, void* v_cache, const void* positions,
                                       const void* slots, const void* cos_t, const void* sin_t, int nh, int nkv, int D,
-                                      int bs, hipStream_t s) {
-  if (N != (nh + 2 * nkv) * D || D % 2 != 0) return -1;
+                                      int bs, const void* bias, hipStream_t s) {
+  if (N != (nh + 2 * nkv) * D || D % 2 != 0 || reinterpret_cast<uintptr_t>(bias) % 4 != 0) return -1;
   if (M < 1 || M > kGemvMaxM || K % kP13UnitElems != 0 || planes == nullptr || hdr == nullptr) return -1;
   RopeEpi rope{(bf16_t*)q_out, q_stride, (bf16_t*)k_cache, (bf16_t*)v_cache, (const int32_t*)positions,
                (const int32_t*)slots, (const float*)cos_t, (const float*)sin_t, nh, nkv, D, bs};
+  rope.bias = static_cast<const bf16_t*>(bias);
   const PackedW pw{static_cast<const uint8_t*>(planes), static_cast<const uint8_t*>(hdr)};
   return gemv_dispatch(M, x, x_stride, norm_w, eps, W, nullptr, 0, N, K, EPI_ROPE, rope, pw, false, s);
 }

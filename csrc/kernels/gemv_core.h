@@ -59,6 +59,9 @@ struct RopeEpi {
   // = dims (d, d + 1); D/2 granules per head
   uint64_t* granules;
   uint32_t gtag;
+  // optional (Qwen2): the q/k/v projection bias [N] bf16 in W's row order (pair-interleaved like
+  // its rows; 4-B aligned), added to the f32 accumulators before the rotation; null = no bias
+  const bf16_t* bias;
 };
 
 // Weight formats of the VALU GEMV. WF_P13: the lossless 13-bit planes of wpack.hip (layout there)
@@ -253,11 +256,17 @@ __device__ __forceinline__ void gemv_block(const int bx, const int by, char* sme
   // dependent cos/sin loads after the prologue, when the position has landed.
   int pre_pos[M], pre_slot[M];
   float pre_c[M], pre_s[M];
+  uint32_t pre_b = 0;  // the pair's two biases (bf16x2: rows 2j, 2j + 1)
   if constexpr (ROPE_PRE) {
 #pragma unroll
     for (int m = 0; m < M; ++m) {
       pre_slot[m] = ld_scalar(rope.slots + m);
       pre_pos[m] = ld_scalar(rope.positions + m);
+    }
+    if (rope.bias != nullptr) {  // launch-uniform; the pair's row is even (N is even: host)
+      const int w_u = __builtin_amdgcn_readfirstlane(wave);
+      const int r_u = min(((bx * WAVES + w_u) * RPW) & ~1, N - 2);
+      pre_b = ld_scalar(reinterpret_cast<const uint32_t*>(rope.bias + r_u));
     }
   }
 
@@ -499,9 +508,10 @@ __device__ __forceinline__ void gemv_block(const int bx, const int by, char* sme
   // paired epilogues (SiLU, RoPE) combine rows (2j, 2j + 1): the same wave holds both when
   // RPW >= 2; with RPW == 1 they sit in waves (w, w + 1) and meet through LDS (PAIR_LDS).
   // RoPE operands of (row n, token m): cos/sin of the pair's frequency and the KV slot
-  auto rope_ops = [&](int n, int m, float& c, float& sn, int& slot) {
+  auto rope_ops = [&](int n, int m, float& c, float& sn, int& slot, uint32_t& b2) {
     const int D = rope.D, half = D / 2;
     slot = rope.slots[m];
+    b2 = rope.bias != nullptr ? *reinterpret_cast<const uint32_t*>(rope.bias + n) : 0u;
     c = 1.f;
     sn = 0.f;
     if (n / D < rope.nh + rope.nkv) {
@@ -511,7 +521,14 @@ __device__ __forceinline__ void gemv_block(const int bx, const int by, char* sme
       sn = rope.sin_t[static_cast<int64_t>(pos) * half + i];
     }
   };
-  auto pair_epi = [&](int n, int m, float v, float x2, float c, float sn, int slot) {
+  // b2: the biases of rows (n, n + 1) (EPI_ROPE with a bias only)
+  auto pair_epi = [&](int n, int m, float v, float x2, float c, float sn, int slot, uint32_t b2) {
+    if constexpr (EPI == EPI_ROPE) {
+      if (rope.bias != nullptr) {  // launch-uniform: a launch without a bias runs the arithmetic it always ran
+        v += bf16_lo(b2);
+        x2 += bf16_hi(b2);
+      }
+    }
     if constexpr (EPI == EPI_SILU) {  // rows (2j, 2j+1) = (gate, up) -> output column n/2
       reinterpret_cast<bf16_t*>(out)[static_cast<int64_t>(m) * out_stride + n / 2] = f32_to_bf16(silu(v) * x2);
     } else if constexpr (EPI == EPI_ROPE) {  // rows (2j, 2j+1) of a Q/K head = dims (i, i + D/2)
@@ -562,9 +579,9 @@ __device__ __forceinline__ void gemv_block(const int bx, const int by, char* sme
       for (int m = 0; m < M; ++m)
         if (lane == m && row0 < N) {
           if constexpr (EPI == EPI_ROPE) {
-            pair_epi(row0, m, acc[0][m], pairx[(wave >> 1) * M + m], pre_c[m], pre_s[m], pre_slot[m]);
+            pair_epi(row0, m, acc[0][m], pairx[(wave >> 1) * M + m], pre_c[m], pre_s[m], pre_slot[m], pre_b);
           } else {
-            pair_epi(row0, m, acc[0][m], pairx[(wave >> 1) * M + m], 1.f, 0.f, -1);
+            pair_epi(row0, m, acc[0][m], pairx[(wave >> 1) * M + m], 1.f, 0.f, -1, 0u);
           }
         }
     }
@@ -643,14 +660,16 @@ __device__ __forceinline__ void gemv_block(const int bx, const int by, char* sme
           if ((r & 1) == 0) {
             float c = 1.f, sn = 0.f;
             int slot = -1;
+            uint32_t b2 = 0;
             if constexpr (EPI == EPI_ROPE && RPW == 2) {  // r == 0: the wave's pair, preloaded
               c = pre_c[m];
               sn = pre_s[m];
               slot = pre_slot[m];
+              b2 = pre_b;
             } else if constexpr (EPI == EPI_ROPE) {
-              rope_ops(n, m, c, sn, slot);
+              rope_ops(n, m, c, sn, slot, b2);
             }
-            pair_epi(n, m, v, acc[r + 1][m], c, sn, slot);
+            pair_epi(n, m, v, acc[r + 1][m], c, sn, slot, b2);
           }
         }
       }

@@ -36,10 +36,11 @@ struct ExpertMap {
   int P = 0, x_div = 1, E = 1;
 };
 
-// Fused epilogue of one lane: rows nb .. nb + 3 (f32 accumulators v) of token m.
+// Fused epilogue of one lane: rows nb .. nb + 3 (f32 accumulators v) of token m. bias4 (EPI_ROPE
+// with rope.bias): the four rows' biases as bf16x2 pairs, added before the rotation.
 template <int EPI>
 __device__ __forceinline__ void gemvm_epilogue(const f32x4& v, int nb, int m, int N, void* __restrict__ out,
-                                               int out_stride, const RopeEpi& rope) {
+                                               int out_stride, const RopeEpi& rope, u32x2 bias4 = u32x2{0u, 0u}) {
   if (nb >= N) return;
   const bool full = nb + 3 < N;
   if constexpr (EPI == EPI_F32) {
@@ -90,7 +91,11 @@ __device__ __forceinline__ void gemvm_epilogue(const f32x4& v, int nb, int m, in
     for (int p = 0; p < 2; ++p) {
       const int n = nb + 2 * p;
       if (n + 1 >= N) continue;
-      const float a = v[2 * p], b = v[2 * p + 1];
+      float a = v[2 * p], b = v[2 * p + 1];
+      if (rope.bias != nullptr) {  // launch-uniform: a launch without a bias runs the arithmetic it always ran
+        a += bf16_lo(bias4[p]);
+        b += bf16_hi(bias4[p]);
+      }
       const int head = n / D;
       if (head < rope.nh + rope.nkv) {
         const int i = (n % D) / 2;
@@ -276,6 +281,19 @@ __global__ __launch_bounds__(S * 64) void gemvm_kernel(const bf16_t* __restrict_
   }
   __syncthreads();
   if (wave != 0) return;
+  // EPI_ROPE with a bias: the lane's four rows' biases per row group, issued ahead of the reduction
+  u32x2 bias4[RB];
+#pragma unroll
+  for (int b = 0; b < RB; ++b) bias4[b] = u32x2{0u, 0u};
+  if constexpr (EPI == EPI_ROPE) {
+    if (rope.bias != nullptr) {
+#pragma unroll
+      for (int b = 0; b < RB; ++b) {
+        const uint32_t* bp = reinterpret_cast<const uint32_t*>(rope.bias + min(n0 + 16 * b + 4 * g, N - 4));  // N % 4 == 0
+        bias4[b] = u32x2{bp[0], bp[1]};
+      }
+    }
+  }
 #pragma unroll
   for (int t = 0; t < TG; ++t) {
     const int m = 16 * t + r;
@@ -293,7 +311,7 @@ __global__ __launch_bounds__(S * 64) void gemvm_kernel(const bf16_t* __restrict_
 #pragma unroll
       for (int w = 1; w < S; ++w) v += red[w][b * TG + t][lane];
       if constexpr (PRO == PRO_NORM) v *= inv;
-      gemvm_epilogue<EPI>(v, n0 + 16 * b + 4 * g, EXP ? pmap[m] : m, N, out, out_stride, rope);
+      gemvm_epilogue<EPI>(v, n0 + 16 * b + 4 * g, EXP ? pmap[m] : m, N, out, out_stride, rope, bias4[b]);
     }
   }
 }

@@ -8,10 +8,15 @@
 // (cdna_hip_programming.md App. B: no on-device trig). Positions and slots are read from device
 // memory, so the same launch is replayable inside a decode HIP graph.
 // KV cache layout: [num_blocks][nkv][bs][D] bf16 (one page = bs contiguous D-rows per head).
+// BIAS (Qwen2): the projection's bias [(nh + 2 nkv) * D] bf16, in the row order of the qkv columns
+// (Q/K pair-interleaved like them), is added in f32 to the bf16 row the GEMM wrote: Q/K before the
+// rotation, V as bf16(f32(v) + f32(b)). An instantiation of its own: a launch without a bias runs
+// the code it always ran.
 #include "common.h"
 
 namespace llmc {
 
+template <bool BIAS>
 __global__ __launch_bounds__(256) void rope_kv_write_kernel(const bf16_t* __restrict__ qkv, int qkv_stride,
                                                             bf16_t* __restrict__ q_out, int q_stride,
                                                             const int32_t* __restrict__ positions,
@@ -19,7 +24,7 @@ __global__ __launch_bounds__(256) void rope_kv_write_kernel(const bf16_t* __rest
                                                             const float* __restrict__ sin_t,
                                                             bf16_t* __restrict__ k_cache, bf16_t* __restrict__ v_cache,
                                                             const int32_t* __restrict__ slots, int nh, int nkv, int D,
-                                                            int bs) {
+                                                            int bs, const bf16_t* __restrict__ bias) {
   const int t = blockIdx.x;
   const int half = D / 2;
   const int quads = half / 4;  // 4 rotation pairs per item
@@ -42,6 +47,14 @@ __global__ __launch_bounds__(256) void rope_kv_write_kernel(const bf16_t* __rest
     const f32x4 s = *reinterpret_cast<const f32x4*>(sr + i);
     float x1[4] = {bf16_lo(pr[0]), bf16_lo(pr[1]), bf16_lo(pr[2]), bf16_lo(pr[3])};
     float x2[4] = {bf16_hi(pr[0]), bf16_hi(pr[1]), bf16_hi(pr[2]), bf16_hi(pr[3])};
+    if constexpr (BIAS) {
+      const u32x4 bp = *reinterpret_cast<const u32x4*>(bias + head * D + 2 * i);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        x1[j] += bf16_lo(bp[j]);
+        x2[j] += bf16_hi(bp[j]);
+      }
+    }
     float o1[4], o2[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -71,7 +84,17 @@ __global__ __launch_bounds__(256) void rope_kv_write_kernel(const bf16_t* __rest
       const int kh = it / (D / 8);
       const int i = (it % (D / 8)) * 8;
       bf16_t* dst = v_cache + ((page * nkv + kh) * bs + off) * D;
-      *reinterpret_cast<u32x4*>(dst + i) = *reinterpret_cast<const u32x4*>(vrow + kh * D + i);
+      u32x4 vv = *reinterpret_cast<const u32x4*>(vrow + kh * D + i);
+      if constexpr (BIAS) {
+        const u32x4 bp = *reinterpret_cast<const u32x4*>(bias + (nh + nkv + kh) * D + i);
+        float f[8], b[8];
+        unpack8(vv, f);
+        unpack8(bp, b);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) f[j] += b[j];
+        vv = pack8(f);
+      }
+      *reinterpret_cast<u32x4*>(dst + i) = vv;
     }
   }
 }
@@ -82,11 +105,11 @@ using namespace llmc;
 
 extern "C" int llmc_rope_kv_write(const void* qkv, int qkv_stride, void* q_out, int q_stride, const void* positions,
                                   const void* cos_t, const void* sin_t, void* k_cache, void* v_cache, const void* slots,
-                                  int T, int nh, int nkv, int D, int bs, hipStream_t s) {
-  if (D % 8 != 0 || (D / 2) % 4 != 0) return -1;
-  rope_kv_write_kernel<<<T, 256, 0, s>>>((const bf16_t*)qkv, qkv_stride, (bf16_t*)q_out, q_stride,
-                                         (const int32_t*)positions, (const float*)cos_t,
-                                         (const float*)sin_t, (bf16_t*)k_cache, (bf16_t*)v_cache,
-                                         (const int32_t*)slots, nh, nkv, D, bs);
+                                  int T, int nh, int nkv, int D, int bs, const void* bias, hipStream_t s) {
+  if (D % 8 != 0 || (D / 2) % 4 != 0 || reinterpret_cast<uintptr_t>(bias) % 16 != 0) return -1;
+  auto kern = bias != nullptr ? rope_kv_write_kernel<true> : rope_kv_write_kernel<false>;
+  kern<<<T, 256, 0, s>>>((const bf16_t*)qkv, qkv_stride, (bf16_t*)q_out, q_stride, (const int32_t*)positions,
+                         (const float*)cos_t, (const float*)sin_t, (bf16_t*)k_cache, (bf16_t*)v_cache,
+                         (const int32_t*)slots, nh, nkv, D, bs, (const bf16_t*)bias);
   return static_cast<int>(hipGetLastError());
 }

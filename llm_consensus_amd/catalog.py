@@ -84,6 +84,7 @@ def describe(name: str, tp: Optional[int] = None) -> Dict:
         "head_dim": c.head_dim, "intermediate": c.intermediate, "vocab": c.vocab,
         "experts": c.n_experts, "top_k": c.top_k_experts,
         **({"sliding_window": c.sliding_window} if c.sliding_window else {}),
+        **({"qkv_bias": True} if c.qkv_bias else {}),
         **({"path": c.checkpoint} if c.checkpoint else {}),
     }
 

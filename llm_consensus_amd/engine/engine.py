@@ -387,7 +387,9 @@ class Engine:
         # their steps). Default: the fused-form buckets of short-qkv shards where attn_oproj does not
         # run; "all": every bucket, ahead of attn_oproj, the long ones as 256-key chunks
         self.qa_plan: List[Optional[tuple]] = [None] * len(self.attn_buckets)
-        if (self.on_gpu and B == 1 and not self.window
+        # (qkv_attn has no place for a q/k/v bias either: Qwen2 models keep qkv_rope + attn_decode,
+        # or attn_oproj, which does not project qkv, where its own check passes)
+        if (self.on_gpu and B == 1 and not self.window and not c.qkv_bias
                 and ops.qkv_attn_supported(self.nh, self.nkv, self.D, c.hidden)):
             self.qa_plan, self.ao_chunks = qkv_attn_plan(self.attn_buckets, self.ao_chunks, str(self.ecfg.qkv_attn),
                                                          (self.nh + 2 * self.nkv) * self.D, self.bs)
@@ -541,7 +543,7 @@ class Engine:
                 xn = ops.rmsnorm(h, Lw.ln1, c.rms_eps)
             qkv = ops.linear(xn, Lw.w_qkv, EPI_BF16)
             ops.rope_kv_write(qkv, pos_d, self.cos_t, self.sin_t, self.k_cache[li], self.v_cache[li], slots_d,
-                              self.nh, self.nkv, self.D, self.bs, qbuf)
+                              self.nh, self.nkv, self.D, self.bs, qbuf, bias=Lw.b_qkv)
             ops.attn_prefill(qbuf, self.k_cache[li], self.v_cache[li], bt, qs_d, ql_d, cl_d, attn, max_qlen,
                              self.nh, self.nkv, self.D, self.bs, self.scale, max_ctx=max_ctx, ksplit=ksplit, kmin=kmin,
                              ws=pws, window=self.window)
@@ -756,7 +758,7 @@ class Engine:
             else:
                 ops.qkv_rope(h, Lw.w_qkv, Lw.ln1, c.rms_eps, q, self.k_cache[li], self.v_cache[li],
                              self.positions[:B], self.slots[:B], self.cos_t, self.sin_t, self.nh, self.nkv, self.D,
-                             self.bs, mfma=self.mfma_decode, Wp=Lw.p_qkv if pk else None)
+                             self.bs, mfma=self.mfma_decode, Wp=Lw.p_qkv if pk else None, bias=Lw.b_qkv)
                 if ao_chunk:  # one-row engines: attention + o_proj + residual (+ TP all-reduce) in one launch
                     routed = self.ao_router[bi] and h.is_cuda  # ... (+ the MoE router)
                     self._attn_oproj(q, li, Lw, h, attn, ao_chunk, routed)

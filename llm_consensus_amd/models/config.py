@@ -24,7 +24,7 @@ class RopeScaling:
 @dataclasses.dataclass(frozen=True)
 class ModelConfig:
     name: str
-    arch: str  # "llama" | "mixtral" | "phi3"
+    arch: str  # "llama" (also Mistral, Qwen2: the same layer layout) | "mixtral" | "phi3"
     n_layers: int
     hidden: int
     n_heads: int
@@ -47,6 +47,9 @@ class ModelConfig:
     # sliding-window attention: position p attends keys (p - W, p]; 0 = every key (one window for
     # all layers)
     sliding_window: int = 0
+    # a bias on the q, k and v projections (Qwen2 / Qwen2.5; o_proj and the MLP have none), added
+    # before the rotation
+    qkv_bias: bool = False
 
     @property
     def eos(self) -> tuple:
@@ -71,7 +74,7 @@ class ModelConfig:
 
     def num_params(self) -> int:
         h, i = self.hidden, self.intermediate
-        attn = h * self.qkv_size + self.q_size * h
+        attn = h * self.qkv_size + self.q_size * h + (self.qkv_size if self.qkv_bias else 0)
         mlp = 3 * h * i * (self.n_experts if self.is_moe else 1)
         router = h * self.n_experts if self.is_moe else 0
         per_layer = attn + mlp + router + 2 * h
@@ -125,6 +128,12 @@ LLAMA_SMALL = ModelConfig("llama-small", "llama", 4, 1024, 8, 2, 128, 2816, 3200
 MIXTRAL_TINY = ModelConfig("mixtral-tiny", "mixtral", 2, 256, 4, 2, 64, 384, 1024, 1000000.0,
                            max_position=4096, n_experts=4, top_k_experts=2)
 PHI3_TINY = ModelConfig("phi3-tiny", "phi3", 2, 192, 2, 2, 96, 384, 1024, 10000.0, max_position=4096)
+QWEN25_7B = ModelConfig("qwen2.5-7b", "llama", 28, 3584, 28, 4, 128, 18944, 152064, 1000000.0, rms_eps=1e-6,
+                        max_position=32768, qkv_bias=True)
+# Qwen2.5's shape class in small: a GQA group of 7 (14 / 2 heads, D = 64), q/k/v biases, every K a
+# multiple of 128, heads / FFN / vocab shardable over TP = 2
+QWEN2_TINY = ModelConfig("qwen2-tiny", "llama", 2, 896, 14, 2, 64, 1024, 1024, 1000000.0, rms_eps=1e-6,
+                         max_position=4096, qkv_bias=True)
 # llama-tiny with a window short enough that tiny prompts cross it
 MISTRAL_TINY = LLAMA_TINY.with_(name="mistral-tiny", sliding_window=48)
 # tiny stand-in for Llama-3-70B in TP=4 rehearsals (heads, kv heads, FFN and vocab shard over 4)
@@ -133,7 +142,7 @@ LLAMA_TINY_TP4 = ModelConfig("llama-tiny-tp4", "llama", 2, 512, 8, 4, 64, 1024, 
 
 FAMILIES = {c.name: c for c in (LLAMA3_8B, LLAMA3_70B, MIXTRAL_8X7B, PHI3_MINI,
                                 LLAMA_TINY, LLAMA_SMALL, MIXTRAL_TINY, PHI3_TINY, LLAMA_TINY_TP4,
-                                MISTRAL_7B, MISTRAL_TINY)}
+                                MISTRAL_7B, MISTRAL_TINY, QWEN25_7B, QWEN2_TINY)}
 
 
 def rope_inv_freq(cfg: ModelConfig):

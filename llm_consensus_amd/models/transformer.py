@@ -5,7 +5,8 @@ checkpoint compatibility:
   * ``w_qkv``  [q + 2 kv, H]  fused Q|K|V rows (one GEMV/GEMM per layer); inside every Q and
     K head the rows are PAIR-INTERLEAVED (row 2i = dim i, row 2i + 1 = dim i + D/2) so the
     rotate-half RoPE pair of a head lands in one wave of the decode GEMV, whose epilogue applies
-    RoPE and writes K/V straight into the paged cache (no separate RoPE launch);
+    RoPE and writes K/V straight into the paged cache (no separate RoPE launch); ``b_qkv``
+    [q + 2 kv] (Qwen2 only) is the projection's bias in the same row order;
   * ``w_o``    [H, q];
   * ``w_gu``   [2 I, H] gate/up rows INTERLEAVED (row 2i = gate_i, 2i + 1 = up_i) so the GEMV
     epilogue produces silu(gate) * up directly and a TP shard is a contiguous row range;
@@ -32,7 +33,9 @@ from .config import ModelConfig
 
 
 class LayerWeights:
-    TENSORS = ("ln1", "ln2", "w_qkv", "w_o", "w_gu", "w_down", "w_router")
+    # b_qkv: the q/k/v projection bias [qkv_size_local] (cfg.qkv_bias; None otherwise), sharded and
+    # pair-interleaved exactly as the rows of w_qkv: b_qkv[n] belongs to w_qkv[n]
+    TENSORS = ("ln1", "ln2", "w_qkv", "w_o", "w_gu", "w_down", "w_router", "b_qkv")
     # p_*: the 13-bit packed twin (ops.wpack.PackedWeight) of w_*, or None: decode streams bf16
     PACKED = ("p_qkv", "p_o", "p_gu", "p_down")
     __slots__ = TENSORS + PACKED
@@ -126,6 +129,18 @@ class TransformerWeights:
                 vs = qkv[c.q_size + c.kv_size + k0 * D:c.q_size + c.kv_size + k1 * D]
                 L.w_qkv = torch.cat([pair_interleave_heads(qs, D), pair_interleave_heads(ks, D), vs], 0).contiguous()
                 del qkv
+                if c.qkv_bias:
+                    # std 1.0, the size of real Qwen2 biases (a zero bias would hide a dropped one);
+                    # qkv is column-parallel, so each rank adds its own slice once
+                    if self.source is not None:
+                        b = self._full(p + "b_qkv", (c.qkv_size,))
+                    else:
+                        b = self._gen(p + "b_qkv", (c.qkv_size,), 1.0)
+                    b = b.view(-1, 1)
+                    bq, bk = b[q0 * D:q1 * D], b[c.q_size + k0 * D:c.q_size + k1 * D]
+                    bv = b[c.q_size + c.kv_size + k0 * D:c.q_size + c.kv_size + k1 * D]
+                    L.b_qkv = torch.cat([pair_interleave_heads(bq, D), pair_interleave_heads(bk, D), bv],
+                                        0).reshape(-1).contiguous()
                 wo = self._linear(p + "w_o", c.hidden, c.q_size)
                 L.w_o = wo[:, q0 * D:q1 * D].contiguous()
                 del wo

@@ -217,38 +217,53 @@ def gemvm(x: torch.Tensor, W: torch.Tensor, epi: int = EPI_BF16, out: Optional[t
     return out
 
 
-def rope_kv_write(qkv, positions, cos_t, sin_t, k_cache, v_cache, slots, nh, nkv, D, bs, q_out) -> None:
+def _qkv_bias(bias, n: int, name: str):
+    """The q/k/v projection bias of a launch: bf16 [n], contiguous, on the GPU (or None)."""
+    if bias is None:
+        return None
+    _bf16(bias, name + ".bias")
+    if not bias.is_cuda or bias.dim() != 1 or bias.numel() != n or not bias.is_contiguous():
+        raise ValueError(f"{name}: bias must be a contiguous GPU tensor of {n} elements, got {tuple(bias.shape)}")
+    return bias
+
+
+def rope_kv_write(qkv, positions, cos_t, sin_t, k_cache, v_cache, slots, nh, nkv, D, bs, q_out, bias=None) -> None:
     """Prefill RoPE: pair-interleaved Q/K rows of ``qkv`` -> canonical rotated q in ``q_out``,
-    rotated k and raw v into the paged cache."""
+    rotated k and raw v into the paged cache. ``bias`` (Qwen2; bf16 [(nh + 2 nkv) D] in the order
+    of the qkv columns): added in f32 to the bf16 row, Q/K before the rotation, V as
+    bf16(f32(v) + f32(b))."""
     if not qkv.is_cuda:
-        oracle.rope_kv_write(qkv, positions, cos_t, sin_t, k_cache, v_cache, slots, nh, nkv, D, bs, q_out)
+        oracle.rope_kv_write(qkv, positions, cos_t, sin_t, k_cache, v_cache, slots, nh, nkv, D, bs, q_out, bias)
         return
     T = qkv.shape[0]
+    bias = _qkv_bias(bias, (nh + 2 * nkv) * D, "rope_kv_write")
     kernels().rope_kv_write(_p(qkv), qkv.stride(0), _p(q_out), q_out.stride(0), _p(positions), _p(cos_t), _p(sin_t),
-                            _p(k_cache), _p(v_cache), _p(slots), T, nh, nkv, D, bs, _s(qkv))
+                            _p(k_cache), _p(v_cache), _p(slots), T, nh, nkv, D, bs, _s(qkv), _p(bias))
 
 
 def qkv_rope(x, W, norm_w, eps, q_out, k_cache, v_cache, positions, slots, cos_t, sin_t, nh, nkv, D, bs,
-             mfma: bool = False, Wp: Optional["wpack.PackedWeight"] = None) -> None:
+             mfma: bool = False, Wp: Optional["wpack.PackedWeight"] = None, bias=None) -> None:
     """Decode qkv projection: fused RMSNorm prologue + RoPE/KV-write epilogue (one launch; form and
-    ``Wp`` as ``linear``)."""
+    ``Wp`` as ``linear``). ``bias`` (Qwen2; bf16 [N], ``bias[n]`` belongs to ``W[n]``): added to the
+    f32 accumulators before the rotation, and on the V rows."""
     if not x.is_cuda:
         qkv = oracle.linear(x, W, EPI_BF16, None, norm_w, eps)
-        oracle.rope_kv_write(qkv, positions, cos_t, sin_t, k_cache, v_cache, slots, nh, nkv, D, bs, q_out)
+        oracle.rope_kv_write(qkv, positions, cos_t, sin_t, k_cache, v_cache, slots, nh, nkv, D, bs, q_out, bias)
         return
     M, K = x.shape
+    bias = _qkv_bias(bias, W.shape[0], "qkv_rope")
     if _use_packed(Wp, M, W.shape[0], K, mfma):
         kernels().gemv_qkv_rope_p13(M, _p(x), x.stride(0), _p(norm_w), float(eps), _p(W), _p(Wp.planes), _p(Wp.hdr),
                                     W.shape[0], K, _p(q_out), q_out.stride(0), _p(k_cache), _p(v_cache),
-                                    _p(positions), _p(slots), _p(cos_t), _p(sin_t), nh, nkv, D, bs, _s(x))
+                                    _p(positions), _p(slots), _p(cos_t), _p(sin_t), nh, nkv, D, bs, _s(x), _p(bias))
         return
     if M > 4 and (K % 128 != 0 or x.stride(0) % 8 != 0):  # outside the MFMA decode form: prefill's path
         qkv = linear(x, W, EPI_BF16, norm_w=norm_w, eps=eps)
-        rope_kv_write(qkv, positions, cos_t, sin_t, k_cache, v_cache, slots, nh, nkv, D, bs, q_out)
+        rope_kv_write(qkv, positions, cos_t, sin_t, k_cache, v_cache, slots, nh, nkv, D, bs, q_out, bias)
         return
     kernels().gemv_qkv_rope(M, _p(x), x.stride(0), _p(norm_w), float(eps), _p(W), W.shape[0], K, _p(q_out),
                             q_out.stride(0), _p(k_cache), _p(v_cache), _p(positions), _p(slots), _p(cos_t), _p(sin_t),
-                            nh, nkv, D, bs, int(mfma), _s(x))
+                            nh, nkv, D, bs, int(mfma), _s(x), _p(bias))
 
 
 FUSED_ATTN_MAX_KEYS = 4096  # decode attention: fused single-launch form up to this bucket capacity

@@ -62,20 +62,28 @@ def rope_tables(inv_freq, max_pos: int):
     return torch.cos(ang).float(), torch.sin(ang).float()
 
 
-def rope_kv_write(qkv, positions, cos_t, sin_t, k_cache, v_cache, slots, nh, nkv, D, bs, q_out):
+def rope_kv_write(qkv, positions, cos_t, sin_t, k_cache, v_cache, slots, nh, nkv, D, bs, q_out, bias=None):
     """qkv rows hold Q and K heads PAIR-INTERLEAVED ([x0, x_h, x1, x_{h+1}, ...], h = D/2);
-    rotated Q goes to ``q_out`` [T, nh*D] in canonical order, rotated K / raw V to the cache."""
+    rotated Q goes to ``q_out`` [T, nh*D] in canonical order, rotated K / raw V to the cache.
+    ``bias`` [(nh + 2 nkv) D] (Qwen2; in the order of the qkv columns) is added in f32 to the row
+    it is given: Q/K before the rotation, V as bf16(f32(v) + f32(b))."""
     T = qkv.shape[0]
     half = D // 2
     pos = positions.long()
     c = cos_t[pos].unsqueeze(1)  # [T,1,half]
     s = sin_t[pos].unsqueeze(1)
-    qk = qkv[:, : (nh + nkv) * D].view(T, nh + nkv, half, 2).float()
+    qkf = qkv[:, : (nh + nkv) * D].float()
+    if bias is not None:
+        qkf = qkf + bias[: (nh + nkv) * D].float()
+    qk = qkf.view(T, nh + nkv, half, 2)
     x1, x2 = qk[..., 0], qk[..., 1]
     rot = torch.cat([x1 * c - x2 * s, x2 * c + x1 * s], dim=-1).to(torch.bfloat16)
     q_out[:, : nh * D] = rot[:, :nh].reshape(T, nh * D)
     if slots is not None:
-        v = qkv[:, (nh + nkv) * D:(nh + 2 * nkv) * D].view(T, nkv, D)
+        v = qkv[:, (nh + nkv) * D:(nh + 2 * nkv) * D]
+        if bias is not None:
+            v = (v.float() + bias[(nh + nkv) * D:(nh + 2 * nkv) * D].float()).to(torch.bfloat16)
+        v = v.view(T, nkv, D)
         for t in range(T):
             sl = int(slots[t])
             if sl < 0:
@@ -295,6 +303,9 @@ def reference_logits(w, cfg, ids, out_pos, cos_t: torch.Tensor, sin_t: torch.Ten
     for L in w.layers:
         xn = rmsnorm(h, L.ln1, cfg.rms_eps)
         qkv = lin(xn, L.w_qkv).to(bf)
+        if getattr(L, "b_qkv", None) is not None:  # Qwen2: f32 add on the stored row, as rope_kv_write
+            qkv = torch.cat([qkv[:, : (nh + nkv) * D].float() + L.b_qkv[: (nh + nkv) * D].float(),
+                             (qkv[:, (nh + nkv) * D:].float() + L.b_qkv[(nh + nkv) * D:].float()).to(bf).float()], 1)
         qk = qkv[:, : (nh + nkv) * D].view(T, nh + nkv, half, 2).float()
         x1, x2 = qk[..., 0], qk[..., 1]
         rot = torch.cat([x1 * cos - x2 * sin, x2 * cos + x1 * sin], dim=-1).to(bf)  # [T, nh + nkv, D]
@@ -362,6 +373,9 @@ def reference_decode_layer(L, cfg, h_in: torch.Tensor, k_cache: torch.Tensor, v_
     G, half = nh // nkv, D // 2
     xn = rmsnorm(h_in, L.ln1, cfg.rms_eps)
     qkv = (xn.float() @ L.w_qkv.float().t()).to(bf)[0]
+    if getattr(L, "b_qkv", None) is not None:  # Qwen2: as reference_logits
+        qkv = torch.cat([qkv[: (nh + nkv) * D].float() + L.b_qkv[: (nh + nkv) * D].float(),
+                         (qkv[(nh + nkv) * D:].float() + L.b_qkv[(nh + nkv) * D:].float()).to(bf).float()])
     qk = qkv[: (nh + nkv) * D].view(nh + nkv, half, 2).float()
     c, sn = cos_t.to(dev)[pos].float(), sin_t.to(dev)[pos].float()
     x1, x2 = qk[..., 0], qk[..., 1]

@@ -39,11 +39,15 @@ def _record(source: str, rid: str, cfg, raw: bool) -> dict:
         rec["path"] = cfg.checkpoint
     if cfg.sliding_window:
         rec["sliding_window"] = cfg.sliding_window
+    if cfg.qkv_bias:
+        rec["qkv_bias"] = True
     if raw:
         d = dataclasses.asdict(cfg)
         d["eos_ids"] = list(d.get("eos_ids") or ())
         if not d.get("sliding_window"):
             d.pop("sliding_window", None)
+        if not d.get("qkv_bias"):
+            d.pop("qkv_bias", None)
         rec["raw"] = d
     return rec
 
