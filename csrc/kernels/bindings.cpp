@@ -28,6 +28,12 @@ int llmc_gemv_qkv_rope_p13(int, const void*, int, const void*, float, const void
                            void*, int, void*, void*, const void*, const void*, const void*, const void*, int, int, int,
                            int, const void*, hipStream_t);
 int llmc_wpack13(const void*, void*, void*, void*, int, int, hipStream_t);
+int llmc_gemv_p12(int, const void*, int, const void*, float, const void*, const void*, const void*, void*, int, int, int,
+                  int, hipStream_t);
+int llmc_gemv_qkv_rope_p12(int, const void*, int, const void*, float, const void*, const void*, const void*, int, int,
+                           void*, int, void*, void*, const void*, const void*, const void*, const void*, int, int, int,
+                           int, const void*, hipStream_t);
+int llmc_wpack12(const void*, void*, void*, void*, int, int, hipStream_t);
 int llmc_gemvm(int, const void*, int, const void*, float, const void*, void*, int, int, int, int, int, hipStream_t);
 int llmc_moe_gemvm(int, const void*, int, const void*, float, const void*, const void*, int, int, void*, int, int, int,
                    int, hipStream_t);
@@ -150,6 +156,25 @@ PYBIND11_MODULE(_llmc_hip, m) {
      py::arg("bias") = 0);  // bias: bf16 [N] in W's row order, 0 = none
   m.def("wpack13", [](ptr W, ptr planes, ptr hdr, ptr raw_count, int N, int K, ptr s) {
     check(llmc_wpack13(P(W), P(planes), P(hdr), P(raw_count), N, K, S(s)), "wpack13");
+  });
+  m.def("gemv_p12", [](int M, ptr x, int xs, ptr nw, float eps, ptr W, ptr planes, ptr recs, ptr out, int os, int N,
+                       int K, int epi, ptr s) {
+    check(llmc_gemv_p12(M, P(x), xs, P(nw), eps, P(W), P(planes), P(recs), P(out), os, N, K, epi, S(s)), "gemv_p12");
+  });
+  m.def("gemv_qkv_rope_p12", [](int M, ptr x, int xs, ptr nw, float eps, ptr W, ptr planes, ptr recs, int N, int K,
+                                ptr qo, int qos, ptr kc, ptr vc, ptr pos, ptr slots, ptr cos_t, ptr sin_t, int nh,
+                                int nkv, int D, int bs, ptr s, ptr bias) {
+    check(llmc_gemv_qkv_rope_p12(M, P(x), xs, P(nw), eps, P(W), P(planes), P(recs), N, K, P(qo), qos, P(kc), P(vc),
+                                 P(pos), P(slots), P(cos_t), P(sin_t), nh, nkv, D, bs, P(bias), S(s)),
+          "gemv_qkv_rope_p12");
+  }, py::arg("M"), py::arg("x"), py::arg("x_stride"), py::arg("norm_w"), py::arg("eps"), py::arg("W"),
+     py::arg("planes"), py::arg("recs"), py::arg("N"), py::arg("K"), py::arg("q_out"), py::arg("q_stride"),
+     py::arg("k_cache"), py::arg("v_cache"), py::arg("positions"), py::arg("slots"), py::arg("cos_t"),
+     py::arg("sin_t"), py::arg("nh"), py::arg("nkv"), py::arg("D"), py::arg("bs"), py::arg("stream"),
+     py::arg("bias") = 0);
+  // counts int32 [2] += (raw rows, exceptions of the packed rows)
+  m.def("wpack12", [](ptr W, ptr planes, ptr recs, ptr counts, int N, int K, ptr s) {
+    check(llmc_wpack12(P(W), P(planes), P(recs), P(counts), N, K, S(s)), "wpack12");
   });
   m.def("moe_gemvm", [](int P, ptr x, int xs, ptr nw, float eps, ptr W, ptr ids, int x_div, int E, ptr out, int os,
                         int N, int K, int epi, ptr s) {

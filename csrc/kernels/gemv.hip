@@ -13,7 +13,7 @@
 
 namespace llmc {
 
-// The 13-bit packed twin of W (gemv_core.h WF_P13), or null planes: the bf16 stream. It rides
+// The 13- or 12-bit packed twin of W (gemv_core.h WF_P13 / WF_P12), or null planes: the bf16 stream. It rides
 // through the launchers as data, so the packed launch picks its geometry by the same code, hence
 // the same blocks and summation order, as the bf16 launch of the same (M, N, K, epilogue).
 template <int M, int NT, int RPW, int PRO, int EPI, int UNROLL>
@@ -45,6 +45,8 @@ static int launch_gemv_g(const void* x, int x_stride, const void* nw, float eps,
                          int out_stride, int N, int K, const RopeEpi& rope, const PackedW& pw, hipStream_t s) {
   constexpr int UNROLL = UNROLL_OVERRIDE ? UNROLL_OVERRIDE : (RPW == 1 ? 4 : (RPW == 2 ? 4 : (M <= 2 ? 4 : 2)));
   constexpr int WAVES = NT / kWave;
+  if (pw.planes != nullptr && pw.wf == WF_P12)  // the chosen geometry as data: gemv_p12.hip holds the P12 kernels
+    return launch_gemv_p12(M, NT, RPW, UNROLL, PRO, EPI, x, x_stride, nw, eps, W, pw, out, out_stride, N, K, rope, s);
   if (pw.planes != nullptr)
     return launch_gemv_p13<M, NT, RPW, PRO, EPI, UNROLL>(x, x_stride, nw, eps, W, pw, out, out_stride, N, K, rope, s);
   auto kern = gemv_kernel<M, NT, RPW, UNROLL, PRO, EPI, false>;
@@ -200,6 +202,19 @@ extern "C" int llmc_gemv_p13(int M, const void* x, int x_stride, const void* nor
   return gemv_dispatch(M, x, x_stride, norm_w, eps, W, out, out_stride, N, K, epi, rope, pw, false, s);
 }
 
+// llmc_gemv_p13 from the 12-bit planes and the row records (`recs`: wpack.hip, the P12 layout).
+extern "C" int llmc_gemv_p12(int M, const void* x, int x_stride, const void* norm_w, float eps, const void* W,
+                             const void* planes, const void* recs, void* out, int out_stride, int N, int K, int epi,
+                             hipStream_t s) {
+  if (epi == EPI_ROPE) return -5;
+  if (M < 1 || M > kGemvMaxM || K % kP13UnitElems != 0 || K > kP12MaxK || planes == nullptr || recs == nullptr ||
+      reinterpret_cast<uintptr_t>(recs) % 4 != 0)
+    return -1;
+  RopeEpi rope{};
+  const PackedW pw{static_cast<const uint8_t*>(planes), static_cast<const uint8_t*>(recs), WF_P12};
+  return gemv_dispatch(M, x, x_stride, norm_w, eps, W, out, out_stride, N, K, epi, rope, pw, false, s);
+}
+
 // qkv projection for decode with fused RMSNorm prologue and RoPE + paged-KV-write epilogue.
 // bias (nullable): the projection's bias [N] bf16 in W's row order, added in f32 before the rotation.
 extern "C" int llmc_gemv_qkv_rope(int M, const void* x, int x_stride, const void* norm_w, float eps, const void* W,
@@ -225,6 +240,23 @@ extern "C" int llmc_gemv_qkv_rope_p13(int M, const void* x, int x_stride, const 
                (const int32_t*)slots, (const float*)cos_t, (const float*)sin_t, nh, nkv, D, bs};
   rope.bias = static_cast<const bf16_t*>(bias);
   const PackedW pw{static_cast<const uint8_t*>(planes), static_cast<const uint8_t*>(hdr)};
+  return gemv_dispatch(M, x, x_stride, norm_w, eps, W, nullptr, 0, N, K, EPI_ROPE, rope, pw, false, s);
+}
+
+// llmc_gemv_qkv_rope for M <= 2 from the 12-bit planes of W (as llmc_gemv_p12).
+extern "C" int llmc_gemv_qkv_rope_p12(int M, const void* x, int x_stride, const void* norm_w, float eps,
+                                      const void* W, const void* planes, const void* recs, int N, int K, void* q_out,
+                                      int q_stride, void* k_cache, void* v_cache, const void* positions,
+                                      const void* slots, const void* cos_t, const void* sin_t, int nh, int nkv, int D,
+                                      int bs, const void* bias, hipStream_t s) {
+  if (N != (nh + 2 * nkv) * D || D % 2 != 0 || reinterpret_cast<uintptr_t>(bias) % 4 != 0) return -1;
+  if (M < 1 || M > kGemvMaxM || K % kP13UnitElems != 0 || K > kP12MaxK || planes == nullptr || recs == nullptr ||
+      reinterpret_cast<uintptr_t>(recs) % 4 != 0)
+    return -1;
+  RopeEpi rope{(bf16_t*)q_out, q_stride, (bf16_t*)k_cache, (bf16_t*)v_cache, (const int32_t*)positions,
+               (const int32_t*)slots, (const float*)cos_t, (const float*)sin_t, nh, nkv, D, bs};
+  rope.bias = static_cast<const bf16_t*>(bias);
+  const PackedW pw{static_cast<const uint8_t*>(planes), static_cast<const uint8_t*>(recs), WF_P12};
   return gemv_dispatch(M, x, x_stride, norm_w, eps, W, nullptr, 0, N, K, EPI_ROPE, rope, pw, false, s);
 }
 

@@ -69,11 +69,23 @@ struct RopeEpi {
 // kP13UnitBytes; a row whose header byte is kP13Raw is read from the bf16 tensor instead. The
 // decoded chunks enter the same dot8_bf16 chain in the same order as the bf16 loop's, so for the
 // same geometry the output bits are the bf16 kernel's.
-enum { WF_BF16 = 0, WF_P13 = 1 };
+//
+// WF_P12: 12 bits per weight (wpack.hip, the P12 layout): the same units without the sign plane
+// (kP12UnitBytes), the sign in the nibble's top bit and a 3-bit exponent code, a window of 16
+// exponents. The few weights of a row outside its window are exceptions: the row's record
+// (kP12RecDwords dwords: header = base | count << 8, or kP12Raw in the low byte, then kP12MaxExc slots
+// value << 16 | k, sorted by k) comes through the scalar cache, and the decoded chunk is patched in
+// the register before the dot product, so it is the bf16 chunk again. A row with more exceptions
+// than slots is raw.
+enum { WF_BF16 = 0, WF_P13 = 1, WF_P12 = 2 };
 constexpr int kP13UnitElems = 2048, kP13UnitBytes = 3328, kP13Raw = 0xff;
+constexpr int kP12UnitBytes = 3072, kP12Raw = 0xff, kP12MaxExc = 16, kP12RecDwords = 1 + kP12MaxExc;
+constexpr int kP12MaxK = 65536 - kP13UnitElems;  // positions are 16 bits, and q = 127 marks the list's end
+constexpr uint32_t kP12End = 0xffffffffu;
 struct PackedW {
-  const uint8_t* planes;  // [N][K / 2048][3328]
-  const uint8_t* hdr;     // [N] (readable up to the next multiple of 4)
+  const uint8_t* planes;  // P13 [N][K / 2048][3328] | P12 [N][K / 2048][3072]
+  const uint8_t* hdr;     // P13 [N] bytes (readable up to the next multiple of 4) | P12 [N][17] dwords
+  int wf = WF_P13;        // host side: which kernel reads it
 };
 struct P13Unit {  // one lane's share of a wave unit: 13 dwords for 32 weights
   u32x4 l0, l1, n;
@@ -96,6 +108,39 @@ __device__ __forceinline__ u32x4 p13_chunk(const P13Unit& p, uint32_t base4) {
   return w;
 }
 
+// The WF_P12 launch of the geometry (NT, RPW, UNROLL) that gemv.hip's launchers chose (gemv_p12.hip: the
+// P12 kernels are a translation unit of their own, compiled beside gemv.hip's); -8: not instantiated.
+int launch_gemv_p12(int M, int NT, int RPW, int UNROLL, int pro, int epi, const void* x, int x_stride, const void* nw,
+                    float eps, const void* W, const PackedW& pw, void* out, int out_stride, int N, int K,
+                    const RopeEpi& rope, hipStream_t s);
+struct P12Unit {  // 12 dwords for 32 weights
+  u32x4 l0, l1, n;
+};
+template <int C>
+__device__ __forceinline__ u32x4 p12_chunk(const P12Unit& p, uint32_t base4) {
+  const uint32_t n = p.n[C];
+  const uint32_t h0 = ((n & 0x07070707u) + base4) | ((n << 4) & 0x80808080u);
+  const uint32_t h1 = (((n >> 4) & 0x07070707u) + base4) | (n & 0x80808080u);
+  const u32x4& L = C < 2 ? p.l0 : p.l1;
+  const uint32_t lw0 = L[(2 * C) & 3], lw1 = L[(2 * C + 1) & 3];
+  u32x4 w;
+  w[0] = __builtin_amdgcn_perm(h0, lw0, 0x05010400u);
+  w[1] = __builtin_amdgcn_perm(h0, lw0, 0x07030602u);
+  w[2] = __builtin_amdgcn_perm(h1, lw1, 0x05010400u);
+  w[3] = __builtin_amdgcn_perm(h1, lw1, 0x07030602u);
+  return w;
+}
+// exception entry `ent` (wave-uniform: value << 16 | q << 9 | lane << 3 | element) into the owning
+// lane's decoded chunk
+__device__ __forceinline__ void p12_patch(u32x4& w, uint32_t ent, int lane) {
+  const bool mine = lane == static_cast<int>((ent >> 3) & 63u);
+  const uint32_t e = ent & 7u, val = ent >> 16;
+  const uint32_t keep = (e & 1u) ? 0x0000ffffu : 0xffff0000u, ins = (e & 1u) ? val << 16 : val;
+#pragma unroll
+  for (int d = 0; d < 4; ++d)
+    if (mine && (e >> 1) == static_cast<uint32_t>(d)) w[d] = (w[d] & keep) | ins;
+}
+
 // Batched decode (3 <= M <= 32 rows): the MFMA form in gemv_mfma.hip, same prologue/epilogues
 // (one 16-token MFMA column group up to 16 rows, two above). This kernel serves M <= kGemvMaxM
 // (and M <= 4 when K is not a multiple of 128). MoE pairs stay within one token group.
@@ -105,14 +150,20 @@ int gemvm_dispatch(int M, const void* x, int x_stride, const void* norm_w, float
 
 // One block of the GEMV (block (bx, by) of its grid; smem = the block's dynamic LDS): the body of
 // gemv_kernel, also the projection role of fused launches (qkv_attn.hip).
-template <int M, int NT, int RPW, int UNROLL, int PRO, int EPI, bool EXPERT = false, int WF = WF_BF16>
+// DEPTH (packed loop): batches in flight ahead of the one being consumed, 1 or 2. The summation
+// order does not depend on it.
+template <int M, int NT, int RPW, int UNROLL, int PRO, int EPI, bool EXPERT = false, int WF = WF_BF16, int DEPTH = 1>
 __device__ __forceinline__ void gemv_block(const int bx, const int by, char* smem, const bf16_t* __restrict__ x,
                                            int x_stride, const bf16_t* __restrict__ norm_w, float eps,
                                            const bf16_t* __restrict__ W, void* __restrict__ out, int out_stride, int N,
                                            int K, const int32_t* __restrict__ expert_ids, int x_div, const RopeEpi& rope,
                                            const CarArgs& ar, const PackedW& pw = PackedW{}) {
   constexpr int WAVES = NT / kWave;
-  constexpr bool P13 = WF == WF_P13;
+  constexpr bool P12 = WF == WF_P12;
+  constexpr bool P13 = WF == WF_P13 || P12;  // the packed loop; P12 differs in the unit, the decode and the patch
+  using PUnit = std::conditional_t<P12, P12Unit, P13Unit>;
+  constexpr int kUnitBytes = P12 ? kP12UnitBytes : kP13UnitBytes;
+  static_assert(DEPTH == 1 || (DEPTH == 2 && P13), "prefetch depth: the packed loop, 1 or 2 batches ahead");
   static_assert(!P13 || (!EXPERT && EPI != EPI_AR && EPI != EPI_COMBINE && UNROLL % 4 == 0 && M <= 2),
                 "packed weights: the dense one- and two-row decode forms");
   constexpr bool PAIR_LDS = (EPI == EPI_SILU || EPI == EPI_ROPE) && RPW == 1;  // host: N % (2 * WAVES) == 0
@@ -196,21 +247,26 @@ __device__ __forceinline__ void gemv_block(const int bx, const int by, char* sme
   // the tail (K is a whole number of units, the last batch maybe not) is masked wave-uniformly.
   constexpr int UB = P13 ? UNROLL / 4 : 1;
   const int units = K / kP13UnitElems;
-  P13Unit cur13[P13 ? RPW : 1][UB];
+  PUnit cur13[P13 ? RPW : 1][UB];
+  PUnit nx13[P13 && DEPTH == 2 ? RPW : 1][UB];  // DEPTH 2: the batch after cur13
   const uint8_t* prow[RPW];
   uint32_t hdr_w[RPW];
-  auto issue13 = [&](P13Unit (&dst)[P13 ? RPW : 1][UB], int ubase) {
+  // P12: the row's record, its next exception entry (kP12End: none left) and that entry's index
+  const uint32_t* rec12[RPW];
+  uint32_t nxt12[RPW], idx12[RPW];
+  auto issue13 = [&](PUnit (&dst)[P13 ? RPW : 1][UB], int ubase) {
 #pragma unroll
     for (int j = 0; j < UB; ++j) {
       const int u = min(ubase + j, units - 1);  // clamped tail: loads stay batched
 #pragma unroll
       for (int r = 0; r < (P13 ? RPW : 1); ++r) {
-        const uint8_t* p = prow[r] + static_cast<int64_t>(u) * kP13UnitBytes + lane * 16;
+        const uint8_t* p = prow[r] + static_cast<int64_t>(u) * kUnitBytes + lane * 16;
         dst[r][j].l0 = load16<true>(p);
         dst[r][j].l1 = load16<true>(p + 1024);
         dst[r][j].n = load16<true>(p + 2048);
         // signs: 4 B per lane at unit + 3072 + 4 lane (p already holds 16 lane)
-        dst[r][j].s = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(p + 3072 - lane * 12));
+        if constexpr (!P12)
+          dst[r][j].s = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(p + 3072 - lane * 12));
       }
     }
   };
@@ -222,10 +278,19 @@ __device__ __forceinline__ void gemv_block(const int bx, const int by, char* sme
 #pragma unroll
     for (int r = 0; r < RPW; ++r) {
       const int n_u = min((bx * WAVES + w_u) * RPW + r, N - 1);
-      hdr_w[r] = ld_scalar(reinterpret_cast<const uint32_t*>(pw.hdr + (n_u & ~3))) >> ((n_u & 3) * 8) & 0xffu;
-      prow[r] = pw.planes + static_cast<int64_t>(n_u) * units * kP13UnitBytes;
+      if constexpr (P12) {  // header and first slot together: no dependent load
+        rec12[r] = reinterpret_cast<const uint32_t*>(pw.hdr) + static_cast<int64_t>(n_u) * kP12RecDwords;
+        hdr_w[r] = ld_scalar(rec12[r]);
+        nxt12[r] = ld_scalar(rec12[r] + 1);
+      } else {
+        hdr_w[r] = ld_scalar(reinterpret_cast<const uint32_t*>(pw.hdr + (n_u & ~3))) >> ((n_u & 3) * 8) & 0xffu;
+      }
+      prow[r] = pw.planes + static_cast<int64_t>(n_u) * units * kUnitBytes;
     }
     issue13(cur13, 0);
+    if constexpr (DEPTH == 2) {
+      if (UB < units) issue13(nx13, UB);  // wave-uniform
+    }
   } else {
     issue(cur, lane);
   }
@@ -445,15 +510,19 @@ __device__ __forceinline__ void gemv_block(const int bx, const int by, char* sme
     uint32_t base4[RPW];
 #pragma unroll
     for (int r = 0; r < RPW; ++r) {
-      raw |= hdr_w[r] == kP13Raw;
-      base4[r] = hdr_w[r] * 0x01010101u;
+      raw |= (hdr_w[r] & 0xffu) == kP13Raw;  // kP12Raw is the same byte
+      base4[r] = (hdr_w[r] & 0xffu) * 0x01010101u;
+      if constexpr (P12) {
+        idx12[r] = 0;
+        if ((hdr_w[r] >> 8 & 0xffu) == 0) nxt12[r] = kP12End;  // slot 0 of an empty list is zero, not an entry
+      }
     }
     if (raw) {  // wave-uniform: a raw row (or its RPW partner) streams the bf16 tensor
       issue(cur, lane);
       stream_bf16();
     } else {
       // chunk c of unit u is the bf16 loop's chunk lane + 64 (4 u + c): same x chunk, same order
-      auto consume13 = [&](const P13Unit (&wv)[RPW][UB], int ubase, auto masked) {
+      auto consume13 = [&](const PUnit (&wv)[RPW][UB], int ubase, auto masked) {
 #pragma unroll
         for (int j = 0; j < UB; ++j) {
           if (!decltype(masked)::value || ubase + j < units) {
@@ -462,7 +531,21 @@ __device__ __forceinline__ void gemv_block(const int bx, const int by, char* sme
               constexpr int C = decltype(cc)::value;
               u32x4 w[RPW];
 #pragma unroll
-              for (int r = 0; r < RPW; ++r) w[r] = p13_chunk<C>(wv[r][j], base4[r]);
+              for (int r = 0; r < RPW; ++r) {
+                if constexpr (P12) {
+                  w[r] = p12_chunk<C>(wv[r][j], base4[r]);
+                  // wave-uniform and rare: entries of this wave chunk (q = k / 512), in k order
+                  const uint32_t q = 4u * static_cast<uint32_t>(ubase + j) + C;
+                  while ((nxt12[r] >> 9 & 0x7fu) == q) {
+                    p12_patch(w[r], nxt12[r], lane);
+                    ++idx12[r];
+                    const uint32_t e = ld_scalar(rec12[r] + 1 + min(idx12[r], static_cast<uint32_t>(kP12MaxExc - 1)));
+                    nxt12[r] = idx12[r] < (hdr_w[r] >> 8 & 0xffu) ? e : kP12End;
+                  }
+                } else {
+                  w[r] = p13_chunk<C>(wv[r][j], base4[r]);
+                }
+              }
 #pragma unroll
               for (int m = 0; m < M; ++m) {
                 const u32x4 xx = xv[m * nchunk + cb + C * kWave];
@@ -480,13 +563,28 @@ __device__ __forceinline__ void gemv_block(const int bx, const int by, char* sme
       const int it13 = (units + UB - 1) / UB;
       int u0 = 0;
       for (int it = 0; it + 1 < it13; ++it, u0 += UB) {
-        P13Unit nxt[RPW][UB];
-        issue13(nxt, u0 + UB);
-        consume13(cur13, u0, Full{});
+        PUnit nxt[RPW][UB];
+        if constexpr (DEPTH == 2) {
+          // two batches ahead; past the row's end nothing is issued (a clamped batch would be bytes
+          // streamed for nothing) and nx13 is not read again
+          const bool more = u0 + 2 * UB < units;  // wave-uniform
+          if (more) issue13(nxt, u0 + 2 * UB);
+          consume13(cur13, u0, Full{});
 #pragma unroll
-        for (int j = 0; j < UB; ++j)
+          for (int j = 0; j < UB; ++j)
 #pragma unroll
-          for (int r = 0; r < RPW; ++r) cur13[r][j] = nxt[r][j];
+            for (int r = 0; r < RPW; ++r) {
+              cur13[r][j] = nx13[r][j];
+              if (more) nx13[r][j] = nxt[r][j];
+            }
+        } else {
+          issue13(nxt, u0 + UB);
+          consume13(cur13, u0, Full{});
+#pragma unroll
+          for (int j = 0; j < UB; ++j)
+#pragma unroll
+            for (int r = 0; r < RPW; ++r) cur13[r][j] = nxt[r][j];
+        }
       }
       if (units % UB == 0) {
         consume13(cur13, u0, Full{});
@@ -698,6 +796,19 @@ __global__ __launch_bounds__(NT) void gemv_p13_kernel(const bf16_t* __restrict__
                                                       RopeEpi rope) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   gemv_block<M, NT, RPW, UNROLL, PRO, EPI, false, WF_P13>(blockIdx.x, blockIdx.y, smem, x, x_stride, norm_w, eps, W,
+                                                          out, out_stride, N, K, nullptr, 1, rope, CarArgs{}, pw);
+}
+
+
+// WF_P12 form (as gemv_p13_kernel; pw.hdr: the rows' records)
+template <int M, int NT, int RPW, int UNROLL, int PRO, int EPI, int DEPTH = 1>
+__global__ __launch_bounds__(NT) void gemv_p12_kernel(const bf16_t* __restrict__ x, int x_stride,
+                                                      const bf16_t* __restrict__ norm_w, float eps,
+                                                      const bf16_t* __restrict__ W, PackedW pw,
+                                                      void* __restrict__ out, int out_stride, int N, int K,
+                                                      RopeEpi rope) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  gemv_block<M, NT, RPW, UNROLL, PRO, EPI, false, WF_P12, DEPTH>(blockIdx.x, blockIdx.y, smem, x, x_stride, norm_w, eps, W,
                                                           out, out_stride, N, K, nullptr, 1, rope, CarArgs{}, pw);
 }
 

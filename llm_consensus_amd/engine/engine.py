@@ -325,9 +325,10 @@ class Engine:
                 why = f"the twin ({need / 2**30:.2f} GiB) does not fit in {free / 2**30:.2f} GiB free"
             else:
                 st = self.w.pack_decode_weights(with_o)
-                log.info("%s: packed weights on: %d of %d tensors, %.2f GiB beside %.2f GiB bf16, raw rows <= %.3f %%",
-                         self.name, st["packed"], st["tensors"], st["bytes"] / 2**30, self.w.nbytes() / 2**30,
-                         100 * st["raw_share"])
+                log.info("%s: packed weights on: %d of %d tensors (%d at 12 bits, %d at 13), %.2f GiB beside %.2f GiB "
+                         "bf16, exceptions %.4f %% of the 12-bit weights, raw rows <= %.3f %%",
+                         self.name, st["packed"], st["tensors"], st["p12"], st["p13"], st["bytes"] / 2**30,
+                         self.w.nbytes() / 2**30, 100 * st["exception_share"], 100 * st["raw_share"])
         if why is not None:
             log.info("%s: packed weights off: %s", self.name, why)
             return

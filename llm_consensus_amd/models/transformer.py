@@ -192,32 +192,47 @@ class TransformerWeights:
         ts = [self.lm_head]
         for L in self.layers:
             ts += [L.w_qkv, L.w_gu, L.w_down] + ([L.w_o] if with_o else [])
-        return sum(wpack.packed_nbytes(*t.shape) for t in ts if t.dim() == 2 and wpack.packable_shape(*t.shape))
+        fmt = wpack.packed_format()
+
+        def size(N, K):
+            return wpack.packed12_nbytes(N, K) if fmt == 12 and wpack.packable12_shape(N, K) else wpack.packed_nbytes(N, K)
+
+        return sum(size(*t.shape) for t in ts if t.dim() == 2 and wpack.packable_shape(*t.shape))
 
     def pack_decode_weights(self, with_o: bool = True) -> dict:
-        """Build the 13-bit packed twins of the decode GEMVs' weights (``ops.wpack``) beside the bf16
-        tensors, which stay (prefill and raw rows read them). A tensor off the unit size, or with
-        more than 1 % raw rows, keeps bf16 only. -> {"tensors", "packed", "bytes", "raw_share"}
-        (the largest share of raw rows among the tensors looked at)."""
+        """Build the packed twins of the decode GEMVs' weights (``ops.wpack.pack_best``: 12-bit, else
+        13-bit) beside the bf16 tensors, which stay (prefill and raw rows read them). A tensor off
+        the unit size, or with more than 1 % raw rows in both formats, keeps bf16 only.
+        -> {"tensors", "packed", "p12", "p13", "bytes", "raw_share" (the largest share of raw rows
+        among the twins), "exception_share" (P12 exceptions over the P12 twins' weights)}."""
         from ..ops import wpack
 
         if self.cfg.is_moe:
             raise ValueError("packed weights: dense models only")
-        st = {"tensors": 0, "packed": 0, "bytes": 0, "raw_share": 0.0}
+        st = {"tensors": 0, "packed": 0, "p12": 0, "p13": 0, "bytes": 0, "raw_share": 0.0, "exception_share": 0.0}
+        exc = w12 = 0
 
         def twin(W):
+            nonlocal exc, w12
             st["tensors"] += 1
-            pw, share = wpack.pack_if_worthwhile(W)
-            st["raw_share"] = max(st["raw_share"], share)
+            pw = wpack.pack_best(W)
             if pw is not None:
                 st["packed"] += 1
                 st["bytes"] += pw.nbytes()
+                st["raw_share"] = max(st["raw_share"], pw.raw_share)
+                if isinstance(pw, wpack.PackedWeight12):
+                    st["p12"] += 1
+                    exc += pw.exceptions
+                    w12 += pw.N * pw.K
+                else:
+                    st["p13"] += 1
             return pw
 
         self.p_lm_head = twin(self.lm_head)
         for L in self.layers:
             L.p_qkv, L.p_gu, L.p_down = twin(L.w_qkv), twin(L.w_gu), twin(L.w_down)
             L.p_o = twin(L.w_o) if with_o else None
+        st["exception_share"] = exc / max(1, w12)
         return st
 
     def packed_nbytes(self) -> int:

@@ -101,7 +101,7 @@ def linear(x: torch.Tensor, W: torch.Tensor, epi: int = EPI_BF16, out: Optional[
     (csrc/kernels/gemm.hip; a norm is a separate rmsnorm launch first).
     Epilogues: bf16 | f32 | EPI_RESADD (accumulates into ``out`` in place) | EPI_SILU (interleaved
     gate/up columns -> silu(g) * u, [M, N / 2]). One code path per shape class, all hand-written.
-    ``Wp``: the 13-bit packed twin of ``W`` (``ops.wpack``); 1-2 rows then stream it instead of
+    ``Wp``: the packed twin of ``W`` (``ops.wpack``: ``PackedWeight12`` or ``PackedWeight``); 1-2 rows then stream it instead of
     ``W`` (fewer bytes, the same output bits), every other row count reads ``W``.
     """
     if not x.is_cuda:
@@ -118,8 +118,9 @@ def linear(x: torch.Tensor, W: torch.Tensor, epi: int = EPI_BF16, out: Optional[
         n_out = N // 2 if epi == EPI_SILU else N
         out = torch.empty(M, n_out, dtype=torch.float32 if epi == EPI_F32 else torch.bfloat16, device=x.device)
     if _use_packed(Wp, M, N, K, mfma):
-        kernels().gemv_p13(M, _p(x), x.stride(0), _p(norm_w), float(eps), _p(W), _p(Wp.planes), _p(Wp.hdr), _p(out),
-                           out.stride(0), N, K, epi, _s(x))
+        gemv_packed = kernels().gemv_p12 if isinstance(Wp, wpack.PackedWeight12) else kernels().gemv_p13
+        gemv_packed(M, _p(x), x.stride(0), _p(norm_w), float(eps), _p(W), _p(Wp.planes), _p(Wp.hdr), _p(out),
+                    out.stride(0), N, K, epi, _s(x))
         return out
     if M <= 4 or (M <= GEMV_MAX_M and K % 128 == 0 and x.stride(0) % 8 == 0):
         kernels().gemv(M, _p(x), x.stride(0), _p(norm_w), float(eps), _p(W), _p(out), out.stride(0), N, K, epi,
@@ -253,9 +254,11 @@ def qkv_rope(x, W, norm_w, eps, q_out, k_cache, v_cache, positions, slots, cos_t
     M, K = x.shape
     bias = _qkv_bias(bias, W.shape[0], "qkv_rope")
     if _use_packed(Wp, M, W.shape[0], K, mfma):
-        kernels().gemv_qkv_rope_p13(M, _p(x), x.stride(0), _p(norm_w), float(eps), _p(W), _p(Wp.planes), _p(Wp.hdr),
-                                    W.shape[0], K, _p(q_out), q_out.stride(0), _p(k_cache), _p(v_cache),
-                                    _p(positions), _p(slots), _p(cos_t), _p(sin_t), nh, nkv, D, bs, _s(x), _p(bias))
+        qkv_packed = (kernels().gemv_qkv_rope_p12 if isinstance(Wp, wpack.PackedWeight12)
+                      else kernels().gemv_qkv_rope_p13)
+        qkv_packed(M, _p(x), x.stride(0), _p(norm_w), float(eps), _p(W), _p(Wp.planes), _p(Wp.hdr),
+                   W.shape[0], K, _p(q_out), q_out.stride(0), _p(k_cache), _p(v_cache),
+                   _p(positions), _p(slots), _p(cos_t), _p(sin_t), nh, nkv, D, bs, _s(x), _p(bias))
         return
     if M > 4 and (K % 128 != 0 or x.stride(0) % 8 != 0):  # outside the MFMA decode form: prefill's path
         qkv = linear(x, W, EPI_BF16, norm_w=norm_w, eps=eps)

@@ -29,6 +29,15 @@ def packed_weights_mode() -> str:
     return {"1": "on", "true": "on", "0": "off", "false": "off"}.get(v, v if v in ("auto", "on", "off") else "auto")
 
 
+def packed_format() -> int:
+    """The packed format tried first, 12 or 13 bits per weight (``ops.wpack.pack_best``): 12 unless
+    LLMC_PACKED_FORMAT=13 (A/B runs)."""
+    v = os.environ.get("LLMC_PACKED_FORMAT", "12").strip()
+    if v not in ("12", "13"):
+        raise ValueError(f"LLMC_PACKED_FORMAT: 12 or 13, got {v!r}")
+    return int(v)
+
+
 @dataclasses.dataclass
 class ModelDemand:
     name: str

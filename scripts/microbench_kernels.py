@@ -193,10 +193,10 @@ def bench_gemv():
 
 
 def bench_packed(shapes=None, rows=(1,), only=None):
-    """The decode GEMVs on the 13-bit packed weight planes against the bf16 stream, each with its
-    real epilogue, on COLD weights (the graph cycles through copies of W beyond the 256 MB MALL, as
-    bench_gemv_sweep). Bytes: bf16 N K 2, packed N K 13 / 8. ``--only qkv,down``: those shapes;
-    ``--rows2``: two rows as well."""
+    """The decode GEMVs on the 13-bit and the 12-bit packed weight planes against the bf16 stream,
+    each with its real epilogue, on COLD weights (the graph cycles through copies of W beyond the
+    256 MB MALL, as bench_gemv_sweep). Bytes: bf16 N K 2, P13 N K 13 / 8, P12 N K 1.5.
+    ``--only qkv,down``: those shapes; ``--rows2``: two rows as well."""
     from llm_consensus_amd.ops import wpack
 
     nh, nkv, D, bs = 32, 8, 128, 64
@@ -208,6 +208,7 @@ def bench_packed(shapes=None, rows=(1,), only=None):
         copies = max(2, (1 << 30) // (N * K * 2))
         Ws = [(torch.randn(N, K, device="cuda") * K ** -0.5).to(BF) for _ in range(copies)]
         Ps = [wpack.pack(W) for W in Ws]
+        Qs = [wpack.pack12(W) for W in Ws]
         nw = torch.ones(K, dtype=BF, device="cuda") if norm else None
         for M in rows:
             x = torch.randn(M, K, device="cuda").to(BF)
@@ -220,27 +221,28 @@ def bench_packed(shapes=None, rows=(1,), only=None):
                 cos_t = torch.ones(16, D // 2, device="cuda")
                 sin_t = torch.zeros(16, D // 2, device="cuda")
 
-                def run(packed):
-                    for W, P in zip(Ws, Ps):
-                        ops.qkv_rope(x, W, nw, 1e-5, q, kc, vc, pos, slots, cos_t, sin_t, nh, nkv, D, bs,
-                                     Wp=P if packed else None)
+                def run(twins):
+                    for W, P in zip(Ws, twins or [None] * copies):
+                        ops.qkv_rope(x, W, nw, 1e-5, q, kc, vc, pos, slots, cos_t, sin_t, nh, nkv, D, bs, Wp=P)
             else:
                 out = torch.zeros(M, N // 2 if epi == 3 else N, dtype=torch.float32 if epi == 1 else BF, device="cuda")
 
-                def run(packed):
-                    for W, P in zip(Ws, Ps):
-                        ops.linear(x, W, epi, out=out, norm_w=nw, Wp=P if packed else None)
+                def run(twins):
+                    for W, P in zip(Ws, twins or [None] * copies):
+                        ops.linear(x, W, epi, out=out, norm_w=nw, Wp=P)
             res = []
-            for _ in range(2):  # alternate the two forms twice: the spread is the noise floor
-                res.append((timeit(lambda: run(False), iters=4, warm=1) / copies,
-                            timeit(lambda: run(True), iters=4, warm=1) / copies))
-            b = min(r[0] for r in res)
-            p = min(r[1] for r in res)
+            for _ in range(2):  # alternate the three forms twice: the spread is the noise floor
+                res.append(tuple(round(timeit(lambda: run(t), iters=4, warm=1) / copies, 3) for t in (None, Ps, Qs)))
+            b, p, q12 = (min(r[i] for r in res) for i in range(3))
+            spread = max(abs(res[0][i] - res[1][i]) / min(res[0][i], res[1][i]) for i in (1, 2))
             gb = N * K * 2 / 1e3
             print(f"packed {name:8s} N={N:6d} K={K:5d} M={M}: bf16 {b:7.2f} us ({gb / b / 1e3:5.2f} TB/s)  "
-                  f"p13 {p:7.2f} us ({gb * 0.8125 / p / 1e3:5.2f} TB/s)  ratio {p / b:.3f}  "
-                  f"raw rows {sum(P.raw_rows for P in Ps)}/{copies * N}  runs {res}", flush=True)
-        del Ws, Ps
+                  f"p13 {p:7.2f} us ({gb * 0.8125 / p / 1e3:5.2f} TB/s) ratio {p / b:.3f}  "
+                  f"p12 {q12:7.2f} us ({gb * 0.75 / q12 / 1e3:5.2f} TB/s) ratio {q12 / b:.3f}  p12/p13 {q12 / p:.3f} "
+                  f"(spread {100 * spread:.1f} %)  raw rows p13 {sum(P.raw_rows for P in Ps)} p12 "
+                  f"{sum(P.raw_rows for P in Qs)} of {copies * N}, exceptions {sum(P.exceptions for P in Qs)}  "
+                  f"runs {res}", flush=True)
+        del Ws, Ps, Qs
         torch.cuda.empty_cache()
 
 
