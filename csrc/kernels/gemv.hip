@@ -202,12 +202,13 @@ extern "C" int llmc_gemv_p13(int M, const void* x, int x_stride, const void* nor
   return gemv_dispatch(M, x, x_stride, norm_w, eps, W, out, out_stride, N, K, epi, rope, pw, false, s);
 }
 
-// llmc_gemv_p13 from the 12-bit planes and the row records (`recs`: wpack.hip, the P12 layout).
+// llmc_gemv_p13 from the 12-bit planes and the row records (`recs`: wpack.hip, the P12 layout). K: whole
+// 2048-weight units, or a multiple of 512 from 2048 up, the planes then with the row tail ("P12 with a tail").
 extern "C" int llmc_gemv_p12(int M, const void* x, int x_stride, const void* norm_w, float eps, const void* W,
                              const void* planes, const void* recs, void* out, int out_stride, int N, int K, int epi,
                              hipStream_t s) {
   if (epi == EPI_ROPE) return -5;
-  if (M < 1 || M > kGemvMaxM || K % kP13UnitElems != 0 || K > kP12MaxK || planes == nullptr || recs == nullptr ||
+  if (M < 1 || M > kGemvMaxM || K % kP12ChunkElems != 0 || K < kP13UnitElems || K > kP12MaxK || planes == nullptr || recs == nullptr ||
       reinterpret_cast<uintptr_t>(recs) % 4 != 0)
     return -1;
   RopeEpi rope{};
@@ -250,7 +251,7 @@ extern "C" int llmc_gemv_qkv_rope_p12(int M, const void* x, int x_stride, const 
                                       const void* slots, const void* cos_t, const void* sin_t, int nh, int nkv, int D,
                                       int bs, const void* bias, hipStream_t s) {
   if (N != (nh + 2 * nkv) * D || D % 2 != 0 || reinterpret_cast<uintptr_t>(bias) % 4 != 0) return -1;
-  if (M < 1 || M > kGemvMaxM || K % kP13UnitElems != 0 || K > kP12MaxK || planes == nullptr || recs == nullptr ||
+  if (M < 1 || M > kGemvMaxM || K % kP12ChunkElems != 0 || K < kP13UnitElems || K > kP12MaxK || planes == nullptr || recs == nullptr ||
       reinterpret_cast<uintptr_t>(recs) % 4 != 0)
     return -1;
   RopeEpi rope{(bf16_t*)q_out, q_stride, (bf16_t*)k_cache, (bf16_t*)v_cache, (const int32_t*)positions,

@@ -77,13 +77,21 @@ struct RopeEpi {
 // value << 16 | k, sorted by k) comes through the scalar cache, and the decoded chunk is patched in
 // the register before the dot product, so it is the bf16 chunk again. A row with more exceptions
 // than slots is raw.
+//
+// WF_P12 with a tail (TAIL; wpack.hip, "P12 with a tail"): K a multiple of 512 (one wave chunk: 64
+// lanes x 8 weights) off the 2048-weight unit. A row is its K / 2048 >= 1 whole units and then tailq =
+// (K / 512) % 4 wave chunks of kP12TailChunkBytes. The tail rides through the packed loop as one more
+// unit slot after the last whole one: its two or three loads fill the slot's registers where p12_chunk
+// expects chunks 0..tailq-1, it is issued one batch ahead like every unit, and its chunks are patched (q =
+// 4 units + c) and summed after the last whole unit's, which is the bf16 loop's order for the lane.
 enum { WF_BF16 = 0, WF_P13 = 1, WF_P12 = 2 };
 constexpr int kP13UnitElems = 2048, kP13UnitBytes = 3328, kP13Raw = 0xff;
 constexpr int kP12UnitBytes = 3072, kP12Raw = 0xff, kP12MaxExc = 16, kP12RecDwords = 1 + kP12MaxExc;
+constexpr int kP12ChunkElems = 512, kP12TailChunkBytes = 768;  // a tail chunk: 512 low bytes, 256 nibble bytes
 constexpr int kP12MaxK = 65536 - kP13UnitElems;  // positions are 16 bits, and q = 127 marks the list's end
 constexpr uint32_t kP12End = 0xffffffffu;
 struct PackedW {
-  const uint8_t* planes;  // P13 [N][K / 2048][3328] | P12 [N][K / 2048][3072]
+  const uint8_t* planes;  // P13 [N][K / 2048][3328] | P12 [N][K / 2048][3072] (+ [(K / 512) % 4][768] per row: the tail)
   const uint8_t* hdr;     // P13 [N] bytes (readable up to the next multiple of 4) | P12 [N][17] dwords
   int wf = WF_P13;        // host side: which kernel reads it
 };
@@ -115,6 +123,9 @@ int launch_gemv_p12(int M, int NT, int RPW, int UNROLL, int pro, int epi, const 
                     const RopeEpi& rope, hipStream_t s);
 struct P12Unit {  // 12 dwords for 32 weights
   u32x4 l0, l1, n;
+};
+struct alignas(4) P12TailN3 {  // a lane's three nibble dwords of a three-chunk tail
+  uint32_t v[3];
 };
 template <int C>
 __device__ __forceinline__ u32x4 p12_chunk(const P12Unit& p, uint32_t base4) {
@@ -152,7 +163,9 @@ int gemvm_dispatch(int M, const void* x, int x_stride, const void* norm_w, float
 // gemv_kernel, also the projection role of fused launches (qkv_attn.hip).
 // DEPTH (packed loop): batches in flight ahead of the one being consumed, 1 or 2. The summation
 // order does not depend on it.
-template <int M, int NT, int RPW, int UNROLL, int PRO, int EPI, bool EXPERT = false, int WF = WF_BF16, int DEPTH = 1>
+// TAIL (WF_P12): K is off the 2048-weight unit and the row ends in (K / 512) % 4 tail chunks.
+template <int M, int NT, int RPW, int UNROLL, int PRO, int EPI, bool EXPERT = false, int WF = WF_BF16, int DEPTH = 1,
+          bool TAIL = false>
 __device__ __forceinline__ void gemv_block(const int bx, const int by, char* smem, const bf16_t* __restrict__ x,
                                            int x_stride, const bf16_t* __restrict__ norm_w, float eps,
                                            const bf16_t* __restrict__ W, void* __restrict__ out, int out_stride, int N,
@@ -164,6 +177,7 @@ __device__ __forceinline__ void gemv_block(const int bx, const int by, char* sme
   using PUnit = std::conditional_t<P12, P12Unit, P13Unit>;
   constexpr int kUnitBytes = P12 ? kP12UnitBytes : kP13UnitBytes;
   static_assert(DEPTH == 1 || (DEPTH == 2 && P13), "prefetch depth: the packed loop, 1 or 2 batches ahead");
+  static_assert(!TAIL || (P12 && DEPTH == 1), "a tail: the 12-bit format, one batch ahead");
   static_assert(!P13 || (!EXPERT && EPI != EPI_AR && EPI != EPI_COMBINE && UNROLL % 4 == 0 && M <= 2),
                 "packed weights: the dense one- and two-row decode forms");
   constexpr bool PAIR_LDS = (EPI == EPI_SILU || EPI == EPI_ROPE) && RPW == 1;  // host: N % (2 * WAVES) == 0
@@ -247,6 +261,7 @@ __device__ __forceinline__ void gemv_block(const int bx, const int by, char* sme
   // the tail (K is a whole number of units, the last batch maybe not) is masked wave-uniformly.
   constexpr int UB = P13 ? UNROLL / 4 : 1;
   const int units = K / kP13UnitElems;
+  const int tailq = TAIL ? (K / kP12ChunkElems) % 4 : 0;  // host: 1..3 under TAIL, and units >= 1
   PUnit cur13[P13 ? RPW : 1][UB];
   PUnit nx13[P13 && DEPTH == 2 ? RPW : 1][UB];  // DEPTH 2: the batch after cur13
   const uint8_t* prow[RPW];
@@ -257,6 +272,43 @@ __device__ __forceinline__ void gemv_block(const int bx, const int by, char* sme
   auto issue13 = [&](PUnit (&dst)[P13 ? RPW : 1][UB], int ubase) {
 #pragma unroll
     for (int j = 0; j < UB; ++j) {
+      if constexpr (TAIL) {
+        if (ubase + j >= units) {  // wave-uniform, as is tailq: the tail's slot (a slot past it loads the tail again and is not read)
+#pragma unroll
+          for (int r = 0; r < RPW; ++r) {
+            const uint8_t* t = prow[r] + static_cast<int64_t>(units) * kUnitBytes;
+            // the unit's registers, truncated: low bytes of chunks 0, 1 in l0, of chunk 2 in l1, nibble dword c in
+            // n[c], fetched with the widest loads the tail's length allows: 2, 2 and 3 loads for 1, 2, 3 chunks.
+            // (Three loads whatever tailq, the 8-B pieces split in two so that the count behind a wait never
+            // depends on this branch, measured slower on every shape: profiles/r11_packed_tail.md section 1.)
+            P12Unit d{};
+            const uint8_t* tn = t + tailq * 512;
+            if (tailq == 1) {
+              const u32x2 lo = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(t + lane * 8));
+              d.l0[0] = lo[0];
+              d.l0[1] = lo[1];
+              d.n[0] = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(tn + lane * 4));
+            } else {
+              d.l0 = load16<true>(t + lane * 16);
+              if (tailq == 2) {
+                const u32x2 nn = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(tn + lane * 8));
+                d.n[0] = nn[0];
+                d.n[1] = nn[1];
+              } else {
+                const u32x2 lo = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(t + 1024 + lane * 8));
+                d.l1[0] = lo[0];
+                d.l1[1] = lo[1];
+                const P12TailN3 nn = *reinterpret_cast<const P12TailN3*>(tn + lane * 12);  // 12 B, 4-B aligned
+                d.n[0] = nn.v[0];
+                d.n[1] = nn.v[1];
+                d.n[2] = nn.v[2];
+              }
+            }
+            dst[r][j] = d;
+          }
+          continue;
+        }
+      }
       const int u = min(ubase + j, units - 1);  // clamped tail: loads stay batched
 #pragma unroll
       for (int r = 0; r < (P13 ? RPW : 1); ++r) {
@@ -286,6 +338,7 @@ __device__ __forceinline__ void gemv_block(const int bx, const int by, char* sme
         hdr_w[r] = ld_scalar(reinterpret_cast<const uint32_t*>(pw.hdr + (n_u & ~3))) >> ((n_u & 3) * 8) & 0xffu;
       }
       prow[r] = pw.planes + static_cast<int64_t>(n_u) * units * kUnitBytes;
+      if constexpr (TAIL) prow[r] += static_cast<int64_t>(n_u) * tailq * kP12TailChunkBytes;  // the row stride with a tail
     }
     issue13(cur13, 0);
     if constexpr (DEPTH == 2) {
@@ -522,13 +575,18 @@ __device__ __forceinline__ void gemv_block(const int bx, const int by, char* sme
       stream_bf16();
     } else {
       // chunk c of unit u is the bf16 loop's chunk lane + 64 (4 u + c): same x chunk, same order
+      // masked: the row's last batch. Its slots past the last whole unit are skipped, but for the tail's
+      // slot (TAIL: slot `units`), of which chunks 0..tailq-1 are summed; all of it is wave-uniform
       auto consume13 = [&](const PUnit (&wv)[RPW][UB], int ubase, auto masked) {
 #pragma unroll
         for (int j = 0; j < UB; ++j) {
-          if (!decltype(masked)::value || ubase + j < units) {
+          const bool part = TAIL && decltype(masked)::value && ubase + j == units;
+          if (!decltype(masked)::value || ubase + j < units || part) {
+            const int live = part ? tailq : 4;  // the slot's chunks
             const int cb = lane + kWave * 4 * (ubase + j);
             auto chunk = [&](auto cc) {
               constexpr int C = decltype(cc)::value;
+              if (TAIL && decltype(masked)::value && C >= live) return;
               u32x4 w[RPW];
 #pragma unroll
               for (int r = 0; r < RPW; ++r) {
@@ -560,7 +618,7 @@ __device__ __forceinline__ void gemv_block(const int bx, const int by, char* sme
           }
         }
       };
-      const int it13 = (units + UB - 1) / UB;
+      const int it13 = (units + (TAIL ? 1 : 0) + UB - 1) / UB;  // TAIL: the tail is one more slot
       int u0 = 0;
       for (int it = 0; it + 1 < it13; ++it, u0 += UB) {
         PUnit nxt[RPW][UB];
@@ -586,7 +644,7 @@ __device__ __forceinline__ void gemv_block(const int bx, const int by, char* sme
             for (int r = 0; r < RPW; ++r) cur13[r][j] = nxt[r][j];
         }
       }
-      if (units % UB == 0) {
+      if (!TAIL && units % UB == 0) {
         consume13(cur13, u0, Full{});
       } else {
         consume13(cur13, u0, Masked{});
@@ -800,15 +858,15 @@ __global__ __launch_bounds__(NT) void gemv_p13_kernel(const bf16_t* __restrict__
 }
 
 
-// WF_P12 form (as gemv_p13_kernel; pw.hdr: the rows' records)
-template <int M, int NT, int RPW, int UNROLL, int PRO, int EPI, int DEPTH = 1>
+// WF_P12 form (as gemv_p13_kernel; pw.hdr: the rows' records); TAIL: for K off the 2048-weight unit
+template <int M, int NT, int RPW, int UNROLL, int PRO, int EPI, int DEPTH = 1, bool TAIL = false>
 __global__ __launch_bounds__(NT) void gemv_p12_kernel(const bf16_t* __restrict__ x, int x_stride,
                                                       const bf16_t* __restrict__ norm_w, float eps,
                                                       const bf16_t* __restrict__ W, PackedW pw,
                                                       void* __restrict__ out, int out_stride, int N, int K,
                                                       RopeEpi rope) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  gemv_block<M, NT, RPW, UNROLL, PRO, EPI, false, WF_P12, DEPTH>(blockIdx.x, blockIdx.y, smem, x, x_stride, norm_w, eps, W,
+  gemv_block<M, NT, RPW, UNROLL, PRO, EPI, false, WF_P12, DEPTH, TAIL>(blockIdx.x, blockIdx.y, smem, x, x_stride, norm_w, eps, W,
                                                           out, out_stride, N, K, nullptr, 1, rope, CarArgs{}, pw);
 }
 

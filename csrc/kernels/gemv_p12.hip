@@ -10,10 +10,10 @@ namespace llmc {
       int N, int K, const RopeEpi &rope, hipStream_t s
 #define LLMC_P12_PASS x, x_stride, nw, eps, W, pw, out, out_stride, N, K, rope, s
 
-template <int M, int NT, int RPW, int UNROLL, int PRO, int EPI, int DEPTH = 1>
+template <int M, int NT, int RPW, int UNROLL, int PRO, int EPI, bool TAIL>
 static int launch_p12(LLMC_P12_ARGS) {
   constexpr int WAVES = NT / kWave;
-  auto kern = gemv_p12_kernel<M, NT, RPW, UNROLL, PRO, EPI, DEPTH>;
+  auto kern = gemv_p12_kernel<M, NT, RPW, UNROLL, PRO, EPI, 1, TAIL>;
   const size_t lds = static_cast<size_t>(M) * K * sizeof(bf16_t) + 2 * M * WAVES * sizeof(float);
   if (lds > 160 * 1024) return -2;
   static bool attr_set = false;
@@ -37,8 +37,19 @@ static int p12_geom(int NT, int RPW, int UNROLL, LLMC_P12_ARGS) {
   if (M == 2 && NT == 1024 && RPW == 1 && UNROLL == 8 && EPI == EPI_ROPE) UNROLL = 4;
   // DEPTH stays 1: two batches ahead (gemv_block's DEPTH = 2) measured slower on every 8B shape but
   // lm_head, where it was equal (profiles/r10_packed12.md §3), so it is not instantiated
-#define LLMC_P12_GEOM(nt, rpw, un) \
-  if (NT == nt && RPW == rpw && UNROLL == un) return launch_p12<M, nt, rpw, un, PRO, EPI>(LLMC_P12_PASS);
+  // A K off the 2048-weight unit runs the TAIL instantiation, a K on it the one without: the tail is a
+  // template flag and not a branch of one kernel, so the kernels of the whole-unit shapes are the code
+  // they were before there was a tail (profiles/r11_packed_tail.md §2)
+  const bool tail = K % kP13UnitElems != 0;
+  // ... and with a tail the two-row, 16-wave, 8-loads form kept 36 B per lane in scratch under every
+  // epilogue (128 VGPRs are its limit): one unit per batch there too, the same order, the same bits
+  if (tail && M == 2 && NT == 1024 && RPW == 1 && UNROLL == 8) UNROLL = 4;
+#define LLMC_P12_GEOM(nt, rpw, un)                                                              \
+  if (NT == nt && RPW == rpw && UNROLL == un) {                                                 \
+    if constexpr (!(M == 2 && nt == 1024 && rpw == 1 && un == 8))                               \
+      if (tail) return launch_p12<M, nt, rpw, un, PRO, EPI, true>(LLMC_P12_PASS);               \
+    return launch_p12<M, nt, rpw, un, PRO, EPI, false>(LLMC_P12_PASS);                          \
+  }
   LLMC_P12_GEOM(1024, 1, 4)
   LLMC_P12_GEOM(896, 1, 4)
   LLMC_P12_GEOM(768, 1, 4)

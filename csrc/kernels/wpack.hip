@@ -112,6 +112,21 @@ __global__ __launch_bounds__(256) void wpack_planes_kernel(const bf16_t* __restr
 // The window: base = max(0, the row's largest e7..e1 - 7), or up to kP12WindowSteps - 1 below it
 // where that leaves fewer exceptions (ties stay with the higher base). Exact zeros, denormals and
 // tiny weights are exceptions; a raw row's codes are taken against base 0.
+//
+// P12 with a tail: K a multiple of 512 (a wave chunk: 64 lanes x 8 weights) off the 2048-weight unit,
+// K > 2048. With U = K / 2048 and Q = (K / 512) % 4 (1..3), a row's planes are its U units as above and then
+// Q * 768 tail bytes (row stride U * 3072 + Q * 768, a multiple of 256). Tail chunk c < Q holds the
+// weights k = 2048 U + 512 c + 8 lane + e. The tail is the unit cut short, a lane's share of each plane
+// contiguous so that it fetches the tail with the widest loads (the layout with one 512-B and one 256-B
+// block per chunk cost two narrow loads per chunk and measured slower than bf16 on the Phi-3 shapes:
+// profiles/r11_packed_tail.md section 1):
+//   [A: 64 x 8 B (Q = 1) | 64 x 16 B]   lane's low bytes of chunk 0 (and of chunk 1), element e at + e
+//   [B: 64 x 8 B, Q = 3 only]           lane's low bytes of chunk 2
+//   [N: 64 x 4 Q B, at Q * 512]         lane's nibble dwords of chunks 0 .. Q-1, byte j of dword c =
+//                                       code(e = j) | code(e = j + 4) << 4, the unit's convention
+// i.e. the registers l0, l1[0..1], n[0..Q-1] of the unit's reader, in 2 (Q = 1, 2) or 3 (Q = 3) loads per
+// lane. The record is the same: the base is chosen over the whole row, and a tail weight outside the
+// window is an entry with q = k / 512 >= 4 U.
 constexpr int kP12WindowSteps = 4;
 
 // one wave per row, scanning the row in k order, so the record's bytes do not depend on timing
@@ -160,7 +175,7 @@ __global__ __launch_bounds__(256) void wpack12_record_kernel(const bf16_t* __res
   if (live && best <= kP12MaxExc) {  // wave-uniform
     int done = 0;
     for (int c0 = 0; c0 < nchunk; c0 += kWave) {  // chunk c0 + lane: k = 8 (c0 + lane) + e, ascending in (c0, lane, e)
-      const u32x4 v = w[c0 + lane];                // K is a multiple of 2048: every lane has a chunk
+      const u32x4 v = w[c0 + lane];                // K is a multiple of 512: every lane has a chunk
       uint32_t m = 0;
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
@@ -197,19 +212,44 @@ __global__ __launch_bounds__(256) void wpack12_record_kernel(const bf16_t* __res
   if (lane < kP12MaxExc) rec[1 + lane] = slots[wv][lane];
 }
 
-// one thread per (row, unit, lane): 4 chunks in, 48 B out
+// one thread per (row, unit, lane): 4 chunks in, 48 B out; with a tail, one more "unit" per row whose
+// threads write the lane's 8 + 4 bytes of each tail chunk
 __global__ __launch_bounds__(256) void wpack12_planes_kernel(const bf16_t* __restrict__ W,
                                                              const uint32_t* __restrict__ recs, uint8_t* __restrict__ P,
                                                              int N, int K) {
-  const int units = K / kP13UnitElems;
+  const int units = K / kP13UnitElems, tailq = (K / kP12ChunkElems) % 4;
+  const int slots = units + (tailq ? 1 : 0);
+  const int64_t row_bytes = static_cast<int64_t>(units) * kP12UnitBytes + tailq * kP12TailChunkBytes;
   const int64_t gid = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (gid >= static_cast<int64_t>(N) * units * kWave) return;
+  if (gid >= static_cast<int64_t>(N) * slots * kWave) return;
   const int lane = static_cast<int>(gid % kWave);
-  const int u = static_cast<int>((gid / kWave) % units);
-  const int64_t row = gid / kWave / units;
+  const int u = static_cast<int>((gid / kWave) % slots);
+  const int64_t row = gid / kWave / slots;
   const u32x4* w = reinterpret_cast<const u32x4*>(W + row * K);
   const uint32_t hb = recs[row * kP12RecDwords] & 0xffu;  // the record kernel ran before on the same stream
   const uint32_t base = hb == kP12Raw ? 0u : hb;
+  if (u == units) {  // the tail: chunk c of the lane is the row's chunk lane + 64 (4 units + c)
+    uint8_t* t = P + row * row_bytes + static_cast<int64_t>(units) * kP12UnitBytes;
+    for (int c = 0; c < tailq; ++c) {
+      const u32x4 v = w[lane + kWave * (4 * units + c)];
+      uint32_t lb[2], cd[2];
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        lb[h] = cd[h] = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const uint32_t b = (v[2 * h + j / 2] >> (16 * (j & 1))) & 0xffffu;
+          lb[h] |= (b & 0xffu) << (8 * j);
+          cd[h] |= (((((b >> 8) & 0x7fu) - base) & 0x7u) | (b >> 15) << 3) << (8 * j);
+        }
+      }
+      // low bytes: chunks 0, 1 in A (8 B per lane with one chunk, else 16), chunk 2 in B
+      uint8_t* lo = c == 2 ? t + 1024 + lane * 8 : t + lane * (tailq == 1 ? 8 : 16) + c * 8;
+      *reinterpret_cast<u32x2*>(lo) = u32x2{lb[0], lb[1]};
+      *reinterpret_cast<uint32_t*>(t + tailq * 512 + (lane * tailq + c) * 4) = cd[0] | (cd[1] << 4);
+    }
+    return;
+  }
   uint32_t lowb[8], nib[4];
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
@@ -229,7 +269,7 @@ __global__ __launch_bounds__(256) void wpack12_planes_kernel(const bf16_t* __res
     }
     nib[c] = code[0] | (code[1] << 4);
   }
-  uint8_t* p = P + (row * units + u) * kP12UnitBytes;
+  uint8_t* p = P + row * row_bytes + static_cast<int64_t>(u) * kP12UnitBytes;
   *reinterpret_cast<u32x4*>(p + lane * 16) = u32x4{lowb[0], lowb[1], lowb[2], lowb[3]};
   *reinterpret_cast<u32x4*>(p + 1024 + lane * 16) = u32x4{lowb[4], lowb[5], lowb[6], lowb[7]};
   *reinterpret_cast<u32x4*>(p + 2048 + lane * 16) = u32x4{nib[0], nib[1], nib[2], nib[3]};
@@ -239,12 +279,12 @@ __global__ __launch_bounds__(256) void wpack12_planes_kernel(const bf16_t* __res
 
 using namespace llmc;
 
-// W bf16 [N, K] (K a multiple of 2048, at most kP12MaxK) -> planes [N, K / 2048, 3072] bytes, recs
-// [N, 17] dwords, counts int32 [2] += (raw rows, exceptions of the packed rows).
+// W bf16 [N, K] (K a multiple of 512 from 2048 up, at most kP12MaxK) -> planes [N, K / 2048 * 3072 +
+// (K / 512) % 4 * 768] bytes, recs [N, 17] dwords, counts int32 [2] += (raw rows, exceptions of the packed rows).
 extern "C" int llmc_wpack12(const void* W, void* planes, void* recs, void* counts, int N, int K, hipStream_t s) {
-  if (N <= 0 || K <= 0 || K % kP13UnitElems != 0 || K > kP12MaxK) return -1;
+  if (N <= 0 || K < kP13UnitElems || K % kP12ChunkElems != 0 || K > kP12MaxK) return -1;
   wpack12_record_kernel<<<(N + 3) / 4, 256, 0, s>>>((const bf16_t*)W, (uint32_t*)recs, (int32_t*)counts, N, K);
-  const int64_t threads = static_cast<int64_t>(N) * (K / kP13UnitElems) * kWave;
+  const int64_t threads = static_cast<int64_t>(N) * ((K + kP13UnitElems - 1) / kP13UnitElems) * kWave;
   wpack12_planes_kernel<<<static_cast<unsigned>((threads + 255) / 256), 256, 0, s>>>(
       (const bf16_t*)W, (const uint32_t*)recs, (uint8_t*)planes, N, K);
   return static_cast<int>(hipGetLastError());

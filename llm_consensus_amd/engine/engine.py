@@ -320,14 +320,15 @@ class Engine:
             need = self.w.packed_demand(with_o)
             free = torch.cuda.mem_get_info(self.device)[0]
             if need == 0:
-                why = "no weight with K a multiple of 2048"
+                why = "no weight the packed formats take (K a multiple of 2048; at 12 bits, of 512 above 2048)"
             elif mode == "auto" and need + PACKED_MARGIN_BYTES > free:
                 why = f"the twin ({need / 2**30:.2f} GiB) does not fit in {free / 2**30:.2f} GiB free"
             else:
                 st = self.w.pack_decode_weights(with_o)
-                log.info("%s: packed weights on: %d of %d tensors (%d at 12 bits, %d at 13), %.2f GiB beside %.2f GiB "
+                log.info("%s: packed weights on: %d of %d tensors (%d at 12 bits, %d of them with a row tail, %d at 13), "
+                         "%.2f GiB beside %.2f GiB "
                          "bf16, exceptions %.4f %% of the 12-bit weights, raw rows <= %.3f %%",
-                         self.name, st["packed"], st["tensors"], st["p12"], st["p13"], st["bytes"] / 2**30,
+                         self.name, st["packed"], st["tensors"], st["p12"], st["tail"], st["p13"], st["bytes"] / 2**30,
                          self.w.nbytes() / 2**30, 100 * st["exception_share"], 100 * st["raw_share"])
         if why is not None:
             log.info("%s: packed weights off: %s", self.name, why)

@@ -86,14 +86,20 @@ class ModelConfig:
     def packed_twin_bytes(self) -> int:
         """Bytes of the 13-bit packed decode twins (ops.wpack) an unsharded dense engine builds beside
         its bf16 weights: 13/16 of every decode GEMV weight whose K is a whole number of 2048-weight
-        units (the o_proj twin counted too: the upper bound); 0 for MoE."""
+        units (the o_proj twin counted too: the upper bound), and the 12-bit twin with a row tail
+        (12/16 and a 68-byte record per row) of every one whose K is another multiple of 512 above
+        2048 (an upper bound as well: ``ops.wpack.TAIL_STAYS_BF16`` leaves a few shapes bf16); 0 for MoE."""
         if self.is_moe:
             return 0
         h, i = self.hidden, self.intermediate
+
+        def twin(n: int, k: int) -> int:
+            if k % 2048 == 0:
+                return n * k * 13 // 8
+            return n * k * 12 // 8 + 68 * n if k % 512 == 0 and k > 2048 else 0
+
         shapes = [(self.qkv_size, h), (h, self.q_size), (2 * i, h), (h, i)]
-        per_layer = sum(n * k for n, k in shapes if k % 2048 == 0)
-        head = self.vocab * h if h % 2048 == 0 else 0
-        return (self.n_layers * per_layer + head) * 13 // 8
+        return self.n_layers * sum(twin(n, k) for n, k in shapes) + twin(self.vocab, h)
 
     def kv_bytes_per_token(self, dtype_bytes: int = 2) -> int:
         return 2 * self.n_layers * self.kv_size * dtype_bytes

@@ -185,8 +185,8 @@ class TransformerWeights:
 
     # -- packed decode twins ---------------------------------------------------------------------
     def packed_demand(self, with_o: bool = True) -> int:
-        """Bytes ``pack_decode_weights`` would allocate (dense models; tensors off the unit size
-        are not packed and cost nothing)."""
+        """Bytes ``pack_decode_weights`` would allocate (dense models; a tensor with K off the
+        2048-weight unit counts its 12-bit twin with a tail where it has one, else nothing)."""
         from ..ops import wpack
 
         ts = [self.lm_head]
@@ -195,21 +195,25 @@ class TransformerWeights:
         fmt = wpack.packed_format()
 
         def size(N, K):
+            if not wpack.packable_shape(N, K):  # off the unit: the 12-bit format with a tail, or nothing
+                return wpack.packed12_tail_nbytes(N, K) if fmt == 12 and wpack.tail_twin_wanted(N, K) else 0
             return wpack.packed12_nbytes(N, K) if fmt == 12 and wpack.packable12_shape(N, K) else wpack.packed_nbytes(N, K)
 
-        return sum(size(*t.shape) for t in ts if t.dim() == 2 and wpack.packable_shape(*t.shape))
+        return sum(size(*t.shape) for t in ts if t.dim() == 2)
 
     def pack_decode_weights(self, with_o: bool = True) -> dict:
         """Build the packed twins of the decode GEMVs' weights (``ops.wpack.pack_best``: 12-bit, else
-        13-bit) beside the bf16 tensors, which stay (prefill and raw rows read them). A tensor off
-        the unit size, or with more than 1 % raw rows in both formats, keeps bf16 only.
-        -> {"tensors", "packed", "p12", "p13", "bytes", "raw_share" (the largest share of raw rows
+        13-bit; 12-bit with a tail for a K off the 2048-weight unit) beside the bf16 tensors, which stay
+        (prefill and raw rows read them). A tensor no format takes, or with more than 1 % raw rows in
+        every format it could have, keeps bf16 only.
+        -> {"tensors", "packed", "p12", "tail" (those of the p12 with a tail), "p13", "bytes", "raw_share" (the largest share of raw rows
         among the twins), "exception_share" (P12 exceptions over the P12 twins' weights)}."""
         from ..ops import wpack
 
         if self.cfg.is_moe:
             raise ValueError("packed weights: dense models only")
-        st = {"tensors": 0, "packed": 0, "p12": 0, "p13": 0, "bytes": 0, "raw_share": 0.0, "exception_share": 0.0}
+        st = {"tensors": 0, "packed": 0, "p12": 0, "tail": 0, "p13": 0, "bytes": 0, "raw_share": 0.0,
+              "exception_share": 0.0}
         exc = w12 = 0
 
         def twin(W):
@@ -222,6 +226,7 @@ class TransformerWeights:
                 st["raw_share"] = max(st["raw_share"], pw.raw_share)
                 if isinstance(pw, wpack.PackedWeight12):
                     st["p12"] += 1
+                    st["tail"] += isinstance(pw, wpack.PackedWeight12Tail)
                     exc += pw.exceptions
                     w12 += pw.N * pw.K
                 else:

@@ -210,6 +210,25 @@ def pack12_reference(W: torch.Tensor) -> PackedWeight12:
     if not packable12_shape(N, K):
         raise ValueError(f"wpack12: K = {K} is not a multiple of {UNIT_ELEMS} up to {MAX_K12}")
     U = K // UNIT_ELEMS
+    bits, rec, raw, cnt, pbase = _records12(W)
+    b = _lane_order(bits, U)
+    low = (b & 0xFF).to(torch.uint8)
+    code = ((((b >> 8) & 0x7F) - pbase.view(N, 1, 1, 1)) & 0x7) | ((b >> 15) << 3)
+    code = code.view(N, U, 64, 4, 2, 4)
+    nib = (code[..., 0, :] | (code[..., 1, :] << 4)).to(torch.uint8)
+    planes = torch.cat([low[..., :16].reshape(N, U, 1024), low[..., 16:].reshape(N, U, 1024),
+                        nib.reshape(N, U, 1024)], dim=2).contiguous()
+    return PackedWeight12(planes, _rec_bytes(rec), int(raw.sum()), int(cnt[~raw].sum()), N, K)
+
+
+def _rec_bytes(rec: torch.Tensor) -> torch.Tensor:
+    return rec.contiguous().view(torch.uint8).view(rec.shape[0], REC12_DWORDS * 4)
+
+
+def _records12(W: torch.Tensor):
+    """(bits int32 [N, K], records int32 [N, 17], raw bool [N], exception counts [N], the base the
+    planes' codes are taken against [N]) of ``W``'s rows, for any K."""
+    N, K = W.shape
     bits = _bits(W)
     hi7 = (bits >> 8) & 0x7F
     bases, counts = window_candidates(W)
@@ -230,15 +249,7 @@ def pack12_reference(W: torch.Tensor) -> PackedWeight12:
         rec[rows, 1 + rank] = (bits[rows, ks].to(torch.int64) << 16) | ks
     rec = (rec - ((rec & 0x80000000) << 1)).to(torch.int32)  # the dword's bits as int32
     pbase = torch.where(raw, torch.zeros_like(base), base)
-    b = _lane_order(bits, U)
-    low = (b & 0xFF).to(torch.uint8)
-    code = ((((b >> 8) & 0x7F) - pbase.view(N, 1, 1, 1)) & 0x7) | ((b >> 15) << 3)
-    code = code.view(N, U, 64, 4, 2, 4)
-    nib = (code[..., 0, :] | (code[..., 1, :] << 4)).to(torch.uint8)
-    planes = torch.cat([low[..., :16].reshape(N, U, 1024), low[..., 16:].reshape(N, U, 1024),
-                        nib.reshape(N, U, 1024)], dim=2).contiguous()
-    hdr = rec.contiguous().view(torch.uint8).view(N, REC12_DWORDS * 4)
-    return PackedWeight12(planes, hdr, int(raw.sum()), int(cnt[~raw].sum()), N, K)
+    return bits, rec, raw, cnt, pbase
 
 
 def unpack12_reference(pw: PackedWeight12, W: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -256,6 +267,16 @@ def unpack12_reference(pw: PackedWeight12, W: Optional[torch.Tensor] = None) -> 
     code = torch.stack([nib & 0xF, nib >> 4], dim=4).reshape(N, U, 64, 32)
     b = ((code >> 3) << 15) | (((code & 7) + base) << 8) | low
     bits = b.view(N, U, 64, 4, 8).permute(0, 1, 3, 2, 4).reshape(N, K).contiguous()
+    return _patched12(pw, bits, W)
+
+
+def _patched12(pw: PackedWeight12, bits: torch.Tensor, W: Optional[torch.Tensor]) -> torch.Tensor:
+    """``bits`` (int32 [N, K], decoded from the planes) with the records' exceptions written in, as
+    bf16; raw rows from ``W``."""
+    N = pw.N
+    rec = pw.records().to(torch.int64) & 0xFFFFFFFF
+    hb = rec[:, 0] & 0xFF
+    raw = hb == RAW
     cnt = torch.where(raw, torch.zeros_like(hb), (rec[:, 0] >> 8) & 0xFF)
     live = torch.arange(MAX_EXC, device=rec.device).view(1, MAX_EXC) < cnt.view(N, 1)
     rows, slot = live.nonzero(as_tuple=True)
@@ -287,6 +308,129 @@ def pack12(W: torch.Tensor) -> PackedWeight12:
     return PackedWeight12(planes, hdr, raw_rows, exceptions, N, K)
 
 
+# ---- P12 with a tail: K a multiple of 512 off the 2048-weight unit ----
+#
+# 512 weights are one wave chunk (64 lanes x 8), the granule of the GEMV's loop and of an exception's
+# position, so a row may end in Q = (K / 512) % 4 = 1..3 chunks after its U = K // 2048 >= 1 whole units:
+# the unit cut short, a lane's share of each plane contiguous (``wpack.hip``): ``A``, the lanes' low bytes
+# of chunks 0 and 1 (8 or 16 per lane); for ``Q`` = 3 ``B``, those of chunk 2 (8 per lane); and at ``Q *
+# 512`` the lanes' ``Q`` nibble dwords (byte j of dword c: ``code[e = j] | code[e = j + 4] << 4``, the
+# unit's convention); the row stride is ``U * 3072 + Q * 768``. Records as above, the base chosen over the
+# whole row.
+
+CHUNK_ELEMS = 512        # weights per wave chunk
+TAIL_CHUNK_BYTES = 768   # 512 low bytes + 256 nibble bytes
+
+
+class PackedWeight12Tail(PackedWeight12):
+    """The 12-bit twin of a bf16 ``[N, K]`` tensor with K off the 2048-weight unit: ``planes`` uint8
+    [N, U * 3072 + Q * 768], every row its whole units and then its tail; the rest as the base class."""
+
+    __slots__ = ()
+
+
+def packable12_tail_shape(N: int, K: int) -> bool:
+    return N > 0 and K % CHUNK_ELEMS == 0 and K % UNIT_ELEMS != 0 and UNIT_ELEMS < K <= MAX_K12
+
+
+# The per-shape choice (profiles/r11_packed_tail.md section 1): catalog shapes on which the tail GEMV,
+# cold and alone, was not faster than the bf16 GEMV by more than the spread of the two runs. They keep
+# streaming bf16: ``pack_best`` builds no twin and ``tail_twin_wanted`` is what ``packed_demand`` asks.
+# (N, K): tail time / bf16 time, spread
+TAIL_STAYS_BF16 = {
+    (3584, 3584): (0.972, 0.032),   # Qwen2.5-7B o_proj: 6.04 against 6.21 us
+    (9216, 3072): (1.016, 0.014),   # Phi-3-mini qkv: 12.05 against 11.87 us
+    (3072, 3072): (1.033, 0.046),   # Phi-3-mini o_proj: 5.25 against 5.08 us
+    (16384, 3072): (1.095, 0.027),  # Phi-3-mini gate_up: 18.93 against 17.28 us
+}
+
+
+def tail_twin_wanted(N: int, K: int) -> bool:
+    """A tail shape that ``pack_best`` packs: every one but the measured losers above."""
+    return packable12_tail_shape(N, K) and (N, K) not in TAIL_STAYS_BF16
+
+
+def _row_bytes12(K: int) -> int:
+    return K // UNIT_ELEMS * UNIT12_BYTES + K % UNIT_ELEMS // CHUNK_ELEMS * TAIL_CHUNK_BYTES
+
+
+def packed12_tail_nbytes(N: int, K: int) -> int:
+    return N * _row_bytes12(K) + N * REC12_DWORDS * 4
+
+
+def _tail_error(shape) -> str:
+    return (f"wpack12 tail: K a multiple of {CHUNK_ELEMS} off the {UNIT_ELEMS}-weight unit, above {UNIT_ELEMS} up to "
+            f"{MAX_K12}, got {tuple(shape)}")
+
+
+def pack12_tail_reference(W: torch.Tensor) -> PackedWeight12Tail:
+    """Plain-torch packer of P12 with a tail (any device), byte for byte what the HIP packer writes."""
+    N, K = W.shape
+    if not packable12_tail_shape(N, K):
+        raise ValueError(_tail_error(W.shape))
+    U, Q = K // UNIT_ELEMS, K % UNIT_ELEMS // CHUNK_ELEMS
+    bits, rec, raw, cnt, pbase = _records12(W)
+    code = ((((bits >> 8) & 0x7F) - pbase.view(N, 1)) & 0x7) | ((bits >> 15) << 3)
+    KU = U * UNIT_ELEMS
+    b = _lane_order(bits[:, :KU].contiguous(), U)
+    cu = _lane_order(code[:, :KU].contiguous(), U).view(N, U, 64, 4, 2, 4)
+    low = (b & 0xFF).to(torch.uint8)
+    nib = (cu[..., 0, :] | (cu[..., 1, :] << 4)).to(torch.uint8)
+    ct = code[:, KU:].reshape(N, Q, 64, 2, 4)                               # [chunk, lane, half, j]
+    tl = (bits[:, KU:] & 0xFF).to(torch.uint8).view(N, Q, 64, 8)            # [chunk, lane, element]
+    QA = min(Q, 2)
+    tail_low = torch.cat([tl[:, :QA].permute(0, 2, 1, 3).reshape(N, QA * 512), tl[:, QA:].reshape(N, (Q - QA) * 512)],
+                         dim=1)                                             # A, B
+    tn = (ct[..., 0, :] | (ct[..., 1, :] << 4)).to(torch.uint8)             # [chunk, lane, j]
+    tail_nib = tn.permute(0, 2, 1, 3).reshape(N, Q * 256)                   # [lane, chunk, j]
+    units = torch.cat([low[..., :16].reshape(N, U, 1024), low[..., 16:].reshape(N, U, 1024),
+                       nib.reshape(N, U, 1024)], dim=2).reshape(N, U * UNIT12_BYTES)
+    planes = torch.cat([units, tail_low, tail_nib], dim=1).contiguous()
+    return PackedWeight12Tail(planes, _rec_bytes(rec), int(raw.sum()), int(cnt[~raw].sum()), N, K)
+
+
+def unpack12_tail_reference(pw: PackedWeight12Tail, W: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``unpack12_reference`` for a twin with a tail."""
+    N, K = pw.N, pw.K
+    U, Q = K // UNIT_ELEMS, K % UNIT_ELEMS // CHUNK_ELEMS
+    p = pw.planes.view(N, _row_bytes12(K)).to(torch.int32)
+    hb = pw.records()[:, 0].to(torch.int32) & 0xFF
+    base = torch.where(hb == RAW, torch.zeros_like(hb), hb)
+    pu = p[:, :U * UNIT12_BYTES].reshape(N, U, UNIT12_BYTES)
+    low = torch.cat([pu[..., :1024].reshape(N, U, 64, 16), pu[..., 1024:2048].reshape(N, U, 64, 16)], dim=3)
+    nib = pu[..., 2048:].reshape(N, U, 64, 4, 4)
+    code = torch.stack([nib & 0xF, nib >> 4], dim=4).reshape(N, U, 64, 32)
+    b = ((code >> 3) << 15) | (((code & 7) + base.view(N, 1, 1, 1)) << 8) | low
+    head = b.view(N, U, 64, 4, 8).permute(0, 1, 3, 2, 4).reshape(N, U * UNIT_ELEMS)
+    pt = p[:, U * UNIT12_BYTES:]
+    tnib = pt[:, Q * 512:].reshape(N, 64, Q, 4).permute(0, 2, 1, 3)          # [chunk, lane, j]
+    tcode = torch.stack([tnib & 0xF, tnib >> 4], dim=3).reshape(N, Q * 512)  # [chunk, lane, half, j] = k order
+    QA = min(Q, 2)
+    tlow = torch.cat([pt[:, :QA * 512].reshape(N, 64, QA, 8).permute(0, 2, 1, 3).reshape(N, QA * 512),
+                      pt[:, QA * 512:Q * 512]], dim=1)                       # A then B -> k order
+    tail = ((tcode >> 3) << 15) | (((tcode & 7) + base.view(N, 1)) << 8) | tlow
+    return _patched12(pw, torch.cat([head, tail], dim=1).contiguous(), W)
+
+
+def pack12_tail(W: torch.Tensor) -> PackedWeight12Tail:
+    """P12-with-a-tail-pack ``W`` where it lives: the HIP packer on the GPU, the reference on the CPU."""
+    if not W.is_cuda:
+        return pack12_tail_reference(W)
+    from ..utils.native import kernels
+
+    N, K = W.shape
+    if W.dtype != torch.bfloat16 or not packable12_tail_shape(N, K):
+        raise ValueError(_tail_error(W.shape) + f" {W.dtype}")
+    W = W.contiguous()
+    planes = torch.empty(N, _row_bytes12(K), dtype=torch.uint8, device=W.device)
+    hdr = torch.empty(N, REC12_DWORDS * 4, dtype=torch.uint8, device=W.device)
+    counts = torch.zeros(2, dtype=torch.int32, device=W.device)
+    kernels().wpack12(W.data_ptr(), planes.data_ptr(), hdr.data_ptr(), counts.data_ptr(), N, K,
+                      torch.cuda.current_stream(W.device).cuda_stream)
+    raw_rows, exceptions = counts.tolist()
+    return PackedWeight12Tail(planes, hdr, raw_rows, exceptions, N, K)
+
+
 def packed_format() -> int:
     """12 or 13: the format ``pack_best`` tries first (``LLMC_PACKED_FORMAT``, A/B runs)."""
     from ..parallel.placement import packed_format as fmt
@@ -296,8 +440,15 @@ def packed_format() -> int:
 
 def pack_best(W: torch.Tensor, fmt: Optional[int] = None):
     """The P12 twin of ``W``; where more than MAX_RAW_SHARE of its rows would be raw (or the shape
-    is off P12's), the P13 twin; where that fails too, None. ``fmt`` 13 skips P12."""
-    if W.dim() != 2 or not packable_shape(*W.shape):
+    is off P12's), the P13 twin; where that fails too, None. ``fmt`` 13 skips P12. A K off the
+    2048-weight unit has the 12-bit format with a tail only (``tail_twin_wanted``: a tail shape that did
+    not measure slower than bf16): that twin, or None where too many rows are raw or ``fmt`` is 13."""
+    if W.dim() != 2:
+        return None
+    if not packable_shape(*W.shape):
+        if (packed_format() if fmt is None else fmt) == 12 and tail_twin_wanted(*W.shape):
+            pwt = pack12_tail(W)
+            return pwt if pwt.raw_share <= MAX_RAW_SHARE else None
         return None
     if (packed_format() if fmt is None else fmt) == 12 and packable12_shape(*W.shape):
         pw12 = pack12(W)

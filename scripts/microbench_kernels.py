@@ -192,24 +192,41 @@ def bench_gemv():
         print(f"gemv N={N:6d} K={K:5d} epi={epi}: {us:8.2f} us  {N * K * 2 / us / 1e6:6.2f} TB/s")
 
 
-def bench_packed(shapes=None, rows=(1,), only=None):
+PACKED_MODELS = {
+    # name: (q heads, kv heads, head dim, [(role, N, K, epilogue, norm prologue, q/k/v bias)])
+    "llama-3-8b": (32, 8, 128, [("qkv", 6144, 4096, 4, True, False), ("o", 4096, 4096, 2, False, False),
+                               ("gate_up", 28672, 4096, 3, True, False), ("down", 4096, 14336, 2, False, False),
+                               ("lm_head", 128256, 4096, 1, True, False)]),
+    "qwen2.5-7b": (28, 4, 128, [("qkv", 4608, 3584, 4, True, True), ("o", 3584, 3584, 2, False, False),
+                               ("gate_up", 37888, 3584, 3, True, False), ("down", 3584, 18944, 2, False, False),
+                               ("lm_head", 152064, 3584, 1, True, False)]),
+    "phi-3-mini": (32, 32, 96, [("qkv", 9216, 3072, 4, True, False), ("o", 3072, 3072, 2, False, False),
+                               ("gate_up", 16384, 3072, 3, True, False), ("down", 3072, 8192, 2, False, False),
+                               ("lm_head", 32064, 3072, 1, True, False)]),
+}
+
+
+def bench_packed(model="llama-3-8b", rows=(1,), only=None):
     """The decode GEMVs on the 13-bit and the 12-bit packed weight planes against the bf16 stream,
     each with its real epilogue, on COLD weights (the graph cycles through copies of W beyond the
-    256 MB MALL, as bench_gemv_sweep). Bytes: bf16 N K 2, P13 N K 13 / 8, P12 N K 1.5.
+    256 MB MALL, as bench_gemv_sweep). Bytes: bf16 N K 2, P13 N K 13 / 8, P12 N K 1.5. A K off the
+    2048-weight unit has the 12-bit form with a row tail only (no P13 column).
+    ``--model qwen2.5-7b|phi-3-mini``: that model's five shapes (default: Llama-3-8B's);
     ``--only qkv,down``: those shapes; ``--rows2``: two rows as well."""
     from llm_consensus_amd.ops import wpack
 
-    nh, nkv, D, bs = 32, 8, 128, 64
-    cases = shapes or [("qkv", 6144, 4096, 4, True), ("o", 4096, 4096, 2, False), ("gate_up", 28672, 4096, 3, True),
-                       ("down", 4096, 14336, 2, False), ("lm_head", 128256, 4096, 1, True)]
-    for name, N, K, epi, norm in cases:
+    nh, nkv, D, cases = PACKED_MODELS[model]
+    bs = 64
+    for name, N, K, epi, norm, with_bias in cases:
         if only and name not in only:
             continue
         copies = max(2, (1 << 30) // (N * K * 2))
         Ws = [(torch.randn(N, K, device="cuda") * K ** -0.5).to(BF) for _ in range(copies)]
-        Ps = [wpack.pack(W) for W in Ws]
-        Qs = [wpack.pack12(W) for W in Ws]
+        tail = wpack.packable12_tail_shape(N, K)
+        Ps = None if tail else [wpack.pack(W) for W in Ws]
+        Qs = [wpack.pack12_tail(W) if tail else wpack.pack12(W) for W in Ws]
         nw = torch.ones(K, dtype=BF, device="cuda") if norm else None
+        bias = torch.randn(N, device="cuda").to(BF) if with_bias else None
         for M in rows:
             x = torch.randn(M, K, device="cuda").to(BF)
             if epi == 4:
@@ -223,23 +240,29 @@ def bench_packed(shapes=None, rows=(1,), only=None):
 
                 def run(twins):
                     for W, P in zip(Ws, twins or [None] * copies):
-                        ops.qkv_rope(x, W, nw, 1e-5, q, kc, vc, pos, slots, cos_t, sin_t, nh, nkv, D, bs, Wp=P)
+                        ops.qkv_rope(x, W, nw, 1e-5, q, kc, vc, pos, slots, cos_t, sin_t, nh, nkv, D, bs, Wp=P, bias=bias)
             else:
                 out = torch.zeros(M, N // 2 if epi == 3 else N, dtype=torch.float32 if epi == 1 else BF, device="cuda")
 
                 def run(twins):
                     for W, P in zip(Ws, twins or [None] * copies):
                         ops.linear(x, W, epi, out=out, norm_w=nw, Wp=P)
+            forms = [None, Qs] if tail else [None, Ps, Qs]
             res = []
-            for _ in range(2):  # alternate the three forms twice: the spread is the noise floor
-                res.append(tuple(round(timeit(lambda: run(t), iters=4, warm=1) / copies, 3) for t in (None, Ps, Qs)))
-            b, p, q12 = (min(r[i] for r in res) for i in range(3))
-            spread = max(abs(res[0][i] - res[1][i]) / min(res[0][i], res[1][i]) for i in (1, 2))
+            for _ in range(2):  # alternate the forms twice: the spread is the noise floor
+                res.append(tuple(round(timeit(lambda: run(t), iters=4, warm=1) / copies, 3) for t in forms))
+            best = [min(r[i] for r in res) for i in range(len(forms))]
+            spread = max(abs(res[0][i] - res[1][i]) / min(res[0][i], res[1][i]) for i in range(len(forms)))
             gb = N * K * 2 / 1e3
-            print(f"packed {name:8s} N={N:6d} K={K:5d} M={M}: bf16 {b:7.2f} us ({gb / b / 1e3:5.2f} TB/s)  "
-                  f"p13 {p:7.2f} us ({gb * 0.8125 / p / 1e3:5.2f} TB/s) ratio {p / b:.3f}  "
-                  f"p12 {q12:7.2f} us ({gb * 0.75 / q12 / 1e3:5.2f} TB/s) ratio {q12 / b:.3f}  p12/p13 {q12 / p:.3f} "
-                  f"(spread {100 * spread:.1f} %)  raw rows p13 {sum(P.raw_rows for P in Ps)} p12 "
+            b, q12 = best[0], best[-1]
+            line = f"packed {name:8s} N={N:6d} K={K:5d} M={M}: bf16 {b:7.2f} us ({gb / b / 1e3:5.2f} TB/s)  "
+            if not tail:
+                p = best[1]
+                line += (f"p13 {p:7.2f} us ({gb * 0.8125 / p / 1e3:5.2f} TB/s) ratio {p / b:.3f}  "
+                         f"p12 {q12:7.2f} us ({gb * 0.75 / q12 / 1e3:5.2f} TB/s) ratio {q12 / b:.3f}  p12/p13 {q12 / p:.3f} ")
+            else:
+                line += f"p12 with a tail {q12:7.2f} us ({gb * 0.75 / q12 / 1e3:5.2f} TB/s) ratio {q12 / b:.3f} "
+            print(line + f"(spread {100 * spread:.1f} %)  raw rows p13 {sum(P.raw_rows for P in Ps or [])} p12 "
                   f"{sum(P.raw_rows for P in Qs)} of {copies * N}, exceptions {sum(P.exceptions for P in Qs)}  "
                   f"runs {res}", flush=True)
         del Ws, Ps, Qs
@@ -572,7 +595,8 @@ if __name__ == "__main__":
     if what in ("sweep",):
         bench_gemv_sweep()
     if what in ("packed",):
-        bench_packed(rows=(1, 2) if "--rows2" in argv else (1,),
+        bench_packed(model=argv[argv.index("--model") + 1] if "--model" in argv else "llama-3-8b",
+                     rows=(1, 2) if "--rows2" in argv else (1,),
                      only=argv[argv.index("--only") + 1].split(",") if "--only" in argv else None)
     if what in ("sweep-phi3",):  # Phi-3-mini shapes (K = 3072 / 8192)
         bench_gemv_sweep([(9216, 3072), (16384, 3072), (3072, 3072), (3072, 8192)])
