@@ -80,6 +80,10 @@ int llmc_moe_gemm(const void*, int, int, const void*, const void*, const void*, 
 int llmc_moe_combine(const void*, const void*, const void*, void*, int, int, int, hipStream_t);
 int llmc_moe_gemv(int, const void*, int, const void*, float, const void*, const void*, int, void*, int, int, int, int,
                   hipStream_t);
+int llmc_moe_gemv_p12(int, const void*, int, const void*, float, const void*, const void*, const void*, const void*, int,
+                      void*, int, int, int, int, hipStream_t);
+int llmc_moe_down_combine_p12(int, const void*, int, const void*, const void*, const void*, const void*, const void*,
+                              void*, int, int, int, int, hipStream_t);
 int llmc_moe_ep_localize(const void*, const void*, int, int, int, void*, void*, hipStream_t);
 int llmc_moe_ep_dispatch(const void*, int, int, int, int, void*, void*, void*, void*, hipStream_t);
 int llmc_gather_rows(const void*, int, const void*, int, int, int, void*, int, hipStream_t);
@@ -320,6 +324,21 @@ PYBIND11_MODULE(_llmc_hip, m) {
   m.def("moe_gemv", [](int npairs, ptr x, int xs, ptr nw, float eps, ptr W, ptr ids, int x_div, ptr out, int os,
                        int N, int K, int epi, ptr s) {
     check(llmc_moe_gemv(npairs, P(x), xs, P(nw), eps, P(W), P(ids), x_div, P(out), os, N, K, epi, S(s)), "moe_gemv");
+  });
+  // the packed expert forms: true = launched; false = no packed kernel for this geometry, nothing launched
+  m.def("moe_gemv_p12", [](int npairs, ptr x, int xs, ptr nw, float eps, ptr W, ptr planes, ptr recs, ptr ids,
+                           int x_div, ptr out, int os, int N, int K, int epi, ptr s) {
+    const int rc = llmc_moe_gemv_p12(npairs, P(x), xs, P(nw), eps, P(W), P(planes), P(recs), P(ids), x_div, P(out), os,
+                                     N, K, epi, S(s));
+    if (rc != -8) check(rc, "moe_gemv_p12");
+    return rc == 0;
+  });
+  m.def("moe_down_combine_p12", [](int T, ptr act, int as, ptr W, ptr planes, ptr recs, ptr ids, ptr w, ptr h, int hs,
+                                   int N, int K, int k, ptr s) {
+    const int rc = llmc_moe_down_combine_p12(T, P(act), as, P(W), P(planes), P(recs), P(ids), P(w), P(h), hs, N, K, k,
+                                             S(s));
+    if (rc != -8) check(rc, "moe_down_combine_p12");
+    return rc == 0;
   });
   m.def("moe_ep_dispatch", [](ptr ids, int npairs, int El, int n, int cap, ptr sp, ptr se, ptr slot, ptr cnt, ptr s) {
     check(llmc_moe_ep_dispatch(P(ids), npairs, El, n, cap, P(sp), P(se), P(slot), P(cnt), S(s)), "moe_ep_dispatch");

@@ -326,8 +326,12 @@ extern "C" int llmc_gemv_ar(int M, const void* x, int x_stride, const void* W, v
 namespace llmc {
 template <int NT, int RPW, int EPI, int PRO>
 static int launch_moe_gemv(int npairs, const void* x, int x_stride, const void* nw, float eps, const void* W,
-                           const void* ids, int x_div, void* out, int out_stride, int N, int K, hipStream_t s) {
+                           const void* ids, int x_div, void* out, int out_stride, int N, int K, const PackedW& pw,
+                           hipStream_t s) {
   constexpr int WAVES = NT / kWave;
+  if (pw.planes != nullptr)  // the chosen geometry as data: gemv_moe_p12.hip holds the packed expert kernels
+    return launch_moe_gemv_p12(NT, RPW, PRO, EPI, npairs, x, x_stride, nw, eps, W, pw, ids, x_div, out, out_stride, N, K,
+                               s);
   const size_t lds = static_cast<size_t>(K) * sizeof(bf16_t) + 2 * WAVES * sizeof(float);
   if (lds > 64 * 1024) return -2;
   dim3 grid((N + WAVES * RPW - 1) / (WAVES * RPW), npairs);
@@ -339,7 +343,8 @@ static int launch_moe_gemv(int npairs, const void* x, int x_stride, const void* 
 
 template <int EPI, int PRO>
 static int moe_gemv_geom(int npairs, const void* x, int x_stride, const void* nw, float eps, const void* W,
-                         const void* ids, int x_div, void* out, int out_stride, int N, int K, hipStream_t s) {
+                         const void* ids, int x_div, void* out, int out_stride, int N, int K, const PackedW& pw,
+                         hipStream_t s) {
   // same geometry rule as the dense GEMV; the grid's y dimension (token, expert) pairs multiplies
   // the rounds, so whole rounds per pair are whole rounds overall. SiLU pairs in one wave where
   // that fills whole rounds (Mixtral's expert gate_up, 28672 rows: 14 waves x 2 rows), as the
@@ -347,18 +352,18 @@ static int moe_gemv_geom(int npairs, const void* x, int x_stride, const void* nw
   static const bool silu_rpw1 = std::getenv("LLMC_GEMV_SILU_RPW1") != nullptr;  // A/B runs only
   if (EPI == EPI_SILU && !silu_rpw1 && K < 8192) {
     if (N % (2 * 16 * 256) == 0)
-      return launch_moe_gemv<1024, 2, EPI, PRO>(npairs, x, x_stride, nw, eps, W, ids, x_div, out, out_stride, N, K, s);
+      return launch_moe_gemv<1024, 2, EPI, PRO>(npairs, x, x_stride, nw, eps, W, ids, x_div, out, out_stride, N, K, pw, s);
     if (N % (2 * 14 * 256) == 0)
-      return launch_moe_gemv<896, 2, EPI, PRO>(npairs, x, x_stride, nw, eps, W, ids, x_div, out, out_stride, N, K, s);
+      return launch_moe_gemv<896, 2, EPI, PRO>(npairs, x, x_stride, nw, eps, W, ids, x_div, out, out_stride, N, K, pw, s);
   }
   switch (pick_waves(N, EPI == EPI_SILU)) {
-    case 16: return launch_moe_gemv<1024, 1, EPI, PRO>(npairs, x, x_stride, nw, eps, W, ids, x_div, out, out_stride, N, K, s);
-    case 14: return launch_moe_gemv<896, 1, EPI, PRO>(npairs, x, x_stride, nw, eps, W, ids, x_div, out, out_stride, N, K, s);
-    case 12: return launch_moe_gemv<768, 1, EPI, PRO>(npairs, x, x_stride, nw, eps, W, ids, x_div, out, out_stride, N, K, s);
-    case 10: return launch_moe_gemv<640, 1, EPI, PRO>(npairs, x, x_stride, nw, eps, W, ids, x_div, out, out_stride, N, K, s);
-    case 8: return launch_moe_gemv<512, 1, EPI, PRO>(npairs, x, x_stride, nw, eps, W, ids, x_div, out, out_stride, N, K, s);
-    case 4: return launch_moe_gemv<256, 1, EPI, PRO>(npairs, x, x_stride, nw, eps, W, ids, x_div, out, out_stride, N, K, s);
-    default: return launch_moe_gemv<256, 2, EPI, PRO>(npairs, x, x_stride, nw, eps, W, ids, x_div, out, out_stride, N, K, s);
+    case 16: return launch_moe_gemv<1024, 1, EPI, PRO>(npairs, x, x_stride, nw, eps, W, ids, x_div, out, out_stride, N, K, pw, s);
+    case 14: return launch_moe_gemv<896, 1, EPI, PRO>(npairs, x, x_stride, nw, eps, W, ids, x_div, out, out_stride, N, K, pw, s);
+    case 12: return launch_moe_gemv<768, 1, EPI, PRO>(npairs, x, x_stride, nw, eps, W, ids, x_div, out, out_stride, N, K, pw, s);
+    case 10: return launch_moe_gemv<640, 1, EPI, PRO>(npairs, x, x_stride, nw, eps, W, ids, x_div, out, out_stride, N, K, pw, s);
+    case 8: return launch_moe_gemv<512, 1, EPI, PRO>(npairs, x, x_stride, nw, eps, W, ids, x_div, out, out_stride, N, K, pw, s);
+    case 4: return launch_moe_gemv<256, 1, EPI, PRO>(npairs, x, x_stride, nw, eps, W, ids, x_div, out, out_stride, N, K, pw, s);
+    default: return launch_moe_gemv<256, 2, EPI, PRO>(npairs, x, x_stride, nw, eps, W, ids, x_div, out, out_stride, N, K, pw, s);
   }
 }
 }  // namespace llmc
@@ -392,22 +397,55 @@ extern "C" int llmc_moe_down_combine(int T, const void* act, int act_stride, con
   return static_cast<int>(hipGetLastError());
 }
 
+namespace llmc {
+static int moe_gemv_entry(int npairs, const void* x, int x_stride, const void* nw, float eps, const void* W,
+                          const void* ids, int x_div, void* out, int out_stride, int N, int K, int epi,
+                          const PackedW& pw, hipStream_t s) {
+  // nw: x is the raw hidden row, RMS-normalised in the prologue (the decode gate_up after the
+  // fused router); nullptr: x is used as is (down projection)
+  if (K % 8 != 0) return -1;
+  switch (epi) {
+    case EPI_BF16:
+      return nw ? moe_gemv_geom<EPI_BF16, PRO_NORM>(npairs, x, x_stride, nw, eps, W, ids, x_div, out, out_stride, N, K, pw, s)
+                : moe_gemv_geom<EPI_BF16, PRO_NONE>(npairs, x, x_stride, nw, eps, W, ids, x_div, out, out_stride, N, K, pw, s);
+    case EPI_SILU:
+      return nw ? moe_gemv_geom<EPI_SILU, PRO_NORM>(npairs, x, x_stride, nw, eps, W, ids, x_div, out, out_stride, N, K, pw, s)
+                : moe_gemv_geom<EPI_SILU, PRO_NONE>(npairs, x, x_stride, nw, eps, W, ids, x_div, out, out_stride, N, K, pw, s);
+    default: return -4;
+  }
+}
+}  // namespace llmc
+
 extern "C" int llmc_moe_gemv(int npairs, const void* x, int x_stride, const void* norm_w, float eps, const void* W,
                              const void* ids, int x_div, void* out, int out_stride, int N, int K, int epi,
                              hipStream_t s) {
-  // norm_w: x is the raw hidden row, RMS-normalised in the prologue (the decode gate_up after the
-  // fused router); nullptr: x is used as is (down projection)
-  if (K % 8 != 0) return -1;
-  const void* nw = norm_w;
-  switch (epi) {
-    case EPI_BF16:
-      return nw ? moe_gemv_geom<EPI_BF16, PRO_NORM>(npairs, x, x_stride, nw, eps, W, ids, x_div, out, out_stride, N, K, s)
-                : moe_gemv_geom<EPI_BF16, PRO_NONE>(npairs, x, x_stride, nw, eps, W, ids, x_div, out, out_stride, N, K, s);
-    case EPI_SILU:
-      return nw ? moe_gemv_geom<EPI_SILU, PRO_NORM>(npairs, x, x_stride, nw, eps, W, ids, x_div, out, out_stride, N, K, s)
-                : moe_gemv_geom<EPI_SILU, PRO_NONE>(npairs, x, x_stride, nw, eps, W, ids, x_div, out, out_stride, N, K, s);
-    default: return -4;
-  }
+  return moe_gemv_entry(npairs, x, x_stride, norm_w, eps, W, ids, x_div, out, out_stride, N, K, epi, PackedW{}, s);
+}
+
+// llmc_moe_gemv with the expert weights streamed from the 12-bit twin of the [E * N, K] view of the stack W
+// (`planes`, `recs`: wpack.hip, the P12 layout; W is read for raw rows). K: whole 2048-weight units. Same
+// geometry, same bits as llmc_moe_gemv; -8: no packed kernel for this geometry or epilogue, nothing was
+// launched (the caller launches llmc_moe_gemv).
+extern "C" int llmc_moe_gemv_p12(int npairs, const void* x, int x_stride, const void* norm_w, float eps, const void* W,
+                                 const void* planes, const void* recs, const void* ids, int x_div, void* out,
+                                 int out_stride, int N, int K, int epi, hipStream_t s) {
+  if (K % kP13UnitElems != 0 || K > kP12MaxK || planes == nullptr || recs == nullptr ||
+      reinterpret_cast<uintptr_t>(recs) % 4 != 0)
+    return -1;
+  const PackedW pw{static_cast<const uint8_t*>(planes), static_cast<const uint8_t*>(recs), WF_P12};
+  return moe_gemv_entry(npairs, x, x_stride, norm_w, eps, W, ids, x_div, out, out_stride, N, K, epi, pw, s);
+}
+
+// llmc_moe_down_combine from the 12-bit twin of W_down's [E * N, K] view (as llmc_moe_gemv_p12): the same
+// fixed geometry, the same bits.
+extern "C" int llmc_moe_down_combine_p12(int T, const void* act, int act_stride, const void* W, const void* planes,
+                                         const void* recs, const void* ids, const void* w, void* h, int h_stride,
+                                         int N, int K, int k, hipStream_t s) {
+  if (k != 2 || K % kP13UnitElems != 0 || K > kP12MaxK || planes == nullptr || recs == nullptr ||
+      reinterpret_cast<uintptr_t>(recs) % 4 != 0)
+    return -1;
+  const PackedW pw{static_cast<const uint8_t*>(planes), static_cast<const uint8_t*>(recs), WF_P12};
+  return launch_moe_combine_p12(T, act, act_stride, W, pw, ids, w, h, h_stride, N, K, s);
 }
 
 // ---- geometry sweep entry (microbenchmarks only: M = 1, fused norm, bf16 out) ----

@@ -121,6 +121,15 @@ __device__ __forceinline__ u32x4 p13_chunk(const P13Unit& p, uint32_t base4) {
 int launch_gemv_p12(int M, int NT, int RPW, int UNROLL, int pro, int epi, const void* x, int x_stride, const void* nw,
                     float eps, const void* W, const PackedW& pw, void* out, int out_stride, int N, int K,
                     const RopeEpi& rope, hipStream_t s);
+// The WF_P12 launches of the MoE decode GEMVs (gemv_moe_p12.hip), pw the twin of the [E * N, K] view of the
+// expert stack W: the pair form in the geometry (NT, RPW) that gemv.hip's moe_gemv_geom chose, and the
+// down projection fused with the top-2 combine in llmc_moe_down_combine's fixed geometry. -8: not
+// instantiated (the caller launches the bf16 kernel: the same bits).
+int launch_moe_gemv_p12(int NT, int RPW, int pro, int epi, int npairs, const void* x, int x_stride, const void* nw,
+                        float eps, const void* W, const PackedW& pw, const void* ids, int x_div, void* out,
+                        int out_stride, int N, int K, hipStream_t s);
+int launch_moe_combine_p12(int T, const void* act, int act_stride, const void* W, const PackedW& pw, const void* ids,
+                           const void* w, void* h, int h_stride, int N, int K, hipStream_t s);
 struct P12Unit {  // 12 dwords for 32 weights
   u32x4 l0, l1, n;
 };
@@ -178,8 +187,11 @@ __device__ __forceinline__ void gemv_block(const int bx, const int by, char* sme
   constexpr int kUnitBytes = P12 ? kP12UnitBytes : kP13UnitBytes;
   static_assert(DEPTH == 1 || (DEPTH == 2 && P13), "prefetch depth: the packed loop, 1 or 2 batches ahead");
   static_assert(!TAIL || (P12 && DEPTH == 1), "a tail: the 12-bit format, one batch ahead");
-  static_assert(!P13 || (!EXPERT && EPI != EPI_AR && EPI != EPI_COMBINE && UNROLL % 4 == 0 && M <= 2),
-                "packed weights: the dense one- and two-row decode forms");
+  static_assert(!P13 || (EPI != EPI_AR && UNROLL % 4 == 0 && M <= 2), "packed weights: the one- and two-row decode forms");
+  // MoE experts (pair form and EPI_COMBINE): the 12-bit twin of the [E * N, K] view of the expert stack, whole
+  // units only, one unit per batch (the only unroll the MoE launchers use)
+  static_assert(!P13 || !EXPERT || (P12 && !TAIL && DEPTH == 1 && UNROLL == 4),
+                "packed expert weights: 12 bits, no tail, one unit per batch");
   constexpr bool PAIR_LDS = (EPI == EPI_SILU || EPI == EPI_ROPE) && RPW == 1;  // host: N % (2 * WAVES) == 0
   // RoPE operands through the scalar cache, early (below): one pair per wave (PAIR_LDS: the even
   // wave's row and its partner; RPW == 2: the wave's own two rows)
@@ -330,15 +342,22 @@ __device__ __forceinline__ void gemv_block(const int bx, const int by, char* sme
 #pragma unroll
     for (int r = 0; r < RPW; ++r) {
       const int n_u = min((bx * WAVES + w_u) * RPW + r, N - 1);
+      int64_t row_u = n_u;  // the row of the twin
+      if constexpr (EXPERT) {
+        // the twin is that of the [E * N, K] view: row n of expert e is its row e * N + n. Pair form: the pair's
+        // expert (>= 0: the exit above); combine: slot r streams row n of its own expert, as wrow[r] does
+        const int e_u = ld_scalar(expert_ids + (COMBINE ? by * RPW + r : by));
+        row_u = static_cast<int64_t>(e_u) * N + (COMBINE ? min(bx * WAVES + w_u, N - 1) : n_u);
+      }
       if constexpr (P12) {  // header and first slot together: no dependent load
-        rec12[r] = reinterpret_cast<const uint32_t*>(pw.hdr) + static_cast<int64_t>(n_u) * kP12RecDwords;
+        rec12[r] = reinterpret_cast<const uint32_t*>(pw.hdr) + row_u * kP12RecDwords;
         hdr_w[r] = ld_scalar(rec12[r]);
         nxt12[r] = ld_scalar(rec12[r] + 1);
       } else {
         hdr_w[r] = ld_scalar(reinterpret_cast<const uint32_t*>(pw.hdr + (n_u & ~3))) >> ((n_u & 3) * 8) & 0xffu;
       }
-      prow[r] = pw.planes + static_cast<int64_t>(n_u) * units * kUnitBytes;
-      if constexpr (TAIL) prow[r] += static_cast<int64_t>(n_u) * tailq * kP12TailChunkBytes;  // the row stride with a tail
+      prow[r] = pw.planes + row_u * units * kUnitBytes;
+      if constexpr (TAIL) prow[r] += row_u * tailq * kP12TailChunkBytes;  // the row stride with a tail
     }
     issue13(cur13, 0);
     if constexpr (DEPTH == 2) {
@@ -608,7 +627,8 @@ __device__ __forceinline__ void gemv_block(const int bx, const int by, char* sme
               for (int m = 0; m < M; ++m) {
                 const u32x4 xx = xv[m * nchunk + cb + C * kWave];
 #pragma unroll
-                for (int r = 0; r < RPW; ++r) acc[r][m] = dot8_bf16(w[r], xx, acc[r][m]);
+                for (int r = 0; r < RPW; ++r)
+                  if (!COMBINE || r == m) acc[r][m] = dot8_bf16(w[r], xx, acc[r][m]);
               }
             };
             chunk(std::integral_constant<int, 0>{});

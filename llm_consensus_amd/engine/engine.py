@@ -96,7 +96,7 @@ class EngineConfig:
     fused_ar: bool = True
     # decode GEMVs of 1-2 rows stream a lossless 13-bit packed twin of their weights (ops.wpack:
     # 0.8125 of the bytes, the same output bits) built beside the bf16 tensors at engine build.
-    # "auto": dense models at TP = 1 on the GPU with max_batch <= 2, when the twin fits in the free
+    # "auto": TP = 1 on the GPU with max_batch <= 2 (a MoE model's expert stacks included), when the twin fits in the free
     # device memory with PACKED_MARGIN_BYTES to spare; "on": the same without the memory check;
     # "off". Environment default (A/B runs): LLMC_PACKED_WEIGHTS.
     packed_weights: str = dataclasses.field(default_factory=packed_weights_mode)
@@ -311,8 +311,8 @@ class Engine:
             why = "switched off"
         elif not self.on_gpu:
             why = "not on a GPU"
-        elif self.cfg.is_moe or self.tp.size != 1:
-            why = "dense models at TP = 1 only"
+        elif self.tp.size != 1:  # hence no expert parallelism either
+            why = "TP = 1 only"
         elif self.ecfg.max_batch > ops.GEMV_PACKED_MAX_M:
             why = f"max_batch {self.ecfg.max_batch} decodes on the MFMA form"
         if why is None and self.w.p_lm_head is None and not any(L.p_qkv or L.p_gu or L.p_down for L in self.w.layers):
@@ -864,14 +864,16 @@ class Engine:
             ops.moe_combine(y, w, ids, h)
             self.tp.all_reduce_(h)
             return
-        ops.moe_gemv(h, Lw.w_gu, ids, k, act, 2 * I_l, H, EPI_SILU, norm_w=Lw.ln2, eps=c.rms_eps)
+        pk = self.packed  # the experts' 12-bit twins (TP = 1, <= 2 rows)
+        ops.moe_gemv(h, Lw.w_gu, ids, k, act, 2 * I_l, H, EPI_SILU, norm_w=Lw.ln2, eps=c.rms_eps,
+                     Wp=Lw.p_gu if pk else None)
         if self.tp.rank != 0:  # row-parallel partial: only rank 0 carries the residual
             h.zero_()
         if k == 2 and not self.w.ep:
             # down projection + combine in one launch (each wave streams its row of both experts)
-            ops.moe_down_combine(act, Lw.w_down, ids, w, h, H, I_l)
+            ops.moe_down_combine(act, Lw.w_down, ids, w, h, H, I_l, Wp=Lw.p_down if pk else None)
         else:
-            ops.moe_gemv(act, Lw.w_down, ids, 1, y, H, I_l, EPI_BF16)
+            ops.moe_gemv(act, Lw.w_down, ids, 1, y, H, I_l, EPI_BF16, Wp=Lw.p_down if pk else None)
             ops.moe_combine(y, w, ids, h)
         self.tp.all_reduce_(h)
 

@@ -88,9 +88,9 @@ class ModelConfig:
         its bf16 weights: 13/16 of every decode GEMV weight whose K is a whole number of 2048-weight
         units (the o_proj twin counted too: the upper bound), and the 12-bit twin with a row tail
         (12/16 and a 68-byte record per row) of every one whose K is another multiple of 512 above
-        2048 (an upper bound as well: ``ops.wpack.TAIL_STAYS_BF16`` leaves a few shapes bf16); 0 for MoE."""
-        if self.is_moe:
-            return 0
+        2048 (an upper bound as well: ``ops.wpack.TAIL_STAYS_BF16`` leaves a few shapes bf16). A MoE model: the
+        dense parts as above (the router has no twin) and the 12-bit twin of each expert stack whose K is a whole
+        number of units (12/16 and a 68-byte record per row; no tail, so nothing for another K)."""
         h, i = self.hidden, self.intermediate
 
         def twin(n: int, k: int) -> int:
@@ -98,8 +98,13 @@ class ModelConfig:
                 return n * k * 13 // 8
             return n * k * 12 // 8 + 68 * n if k % 512 == 0 and k > 2048 else 0
 
-        shapes = [(self.qkv_size, h), (h, self.q_size), (2 * i, h), (h, i)]
-        return self.n_layers * sum(twin(n, k) for n, k in shapes) + twin(self.vocab, h)
+        def experts(n: int, k: int) -> int:
+            rows = self.n_experts * n
+            return rows * k * 12 // 8 + 68 * rows if k % 2048 == 0 and k <= 65536 - 2048 else 0
+
+        shapes = [(self.qkv_size, h), (h, self.q_size)]
+        ffn = experts(2 * i, h) + experts(h, i) if self.is_moe else twin(2 * i, h) + twin(h, i)
+        return self.n_layers * (sum(twin(n, k) for n, k in shapes) + ffn) + twin(self.vocab, h)
 
     def kv_bytes_per_token(self, dtype_bytes: int = 2) -> int:
         return 2 * self.n_layers * self.kv_size * dtype_bytes

@@ -36,7 +36,8 @@ class LayerWeights:
     # b_qkv: the q/k/v projection bias [qkv_size_local] (cfg.qkv_bias; None otherwise), sharded and
     # pair-interleaved exactly as the rows of w_qkv: b_qkv[n] belongs to w_qkv[n]
     TENSORS = ("ln1", "ln2", "w_qkv", "w_o", "w_gu", "w_down", "w_router", "b_qkv")
-    # p_*: the 13-bit packed twin (ops.wpack.PackedWeight) of w_*, or None: decode streams bf16
+    # p_*: the packed twin (ops.wpack: PackedWeight / PackedWeight12; PackedExperts12 of a MoE layer's w_gu and
+    # w_down stacks) of w_*, or None: decode streams bf16
     PACKED = ("p_qkv", "p_o", "p_gu", "p_down")
     __slots__ = TENSORS + PACKED
 
@@ -185,8 +186,9 @@ class TransformerWeights:
 
     # -- packed decode twins ---------------------------------------------------------------------
     def packed_demand(self, with_o: bool = True) -> int:
-        """Bytes ``pack_decode_weights`` would allocate (dense models; a tensor with K off the
-        2048-weight unit counts its 12-bit twin with a tail where it has one, else nothing)."""
+        """Bytes ``pack_decode_weights`` would allocate (a tensor with K off the 2048-weight unit counts
+        its 12-bit twin with a tail where it has one, else nothing; a MoE layer's expert stacks their 12-bit
+        twins on whole units, the router nothing)."""
         from ..ops import wpack
 
         ts = [self.lm_head]
@@ -199,19 +201,21 @@ class TransformerWeights:
                 return wpack.packed12_tail_nbytes(N, K) if fmt == 12 and wpack.tail_twin_wanted(N, K) else 0
             return wpack.packed12_nbytes(N, K) if fmt == 12 and wpack.packable12_shape(N, K) else wpack.packed_nbytes(N, K)
 
-        return sum(size(*t.shape) for t in ts if t.dim() == 2)
+        def experts(E, N, K):
+            return wpack.packed12_nbytes(E * N, K) if fmt == 12 and wpack.expert_twin_wanted(N, K) else 0
+
+        return sum(size(*t.shape) if t.dim() == 2 else experts(*t.shape) for t in ts if t.dim() in (2, 3))
 
     def pack_decode_weights(self, with_o: bool = True) -> dict:
         """Build the packed twins of the decode GEMVs' weights (``ops.wpack.pack_best``: 12-bit, else
-        13-bit; 12-bit with a tail for a K off the 2048-weight unit) beside the bf16 tensors, which stay
+        13-bit; 12-bit with a tail for a K off the 2048-weight unit; a MoE layer's expert stacks ``w_gu`` /
+        ``w_down`` at 12 bits on whole units, its router stays bf16) beside the bf16 tensors, which stay
         (prefill and raw rows read them). A tensor no format takes, or with more than 1 % raw rows in
         every format it could have, keeps bf16 only.
-        -> {"tensors", "packed", "p12", "tail" (those of the p12 with a tail), "p13", "bytes", "raw_share" (the largest share of raw rows
+        -> {"tensors", "packed", "p12" (expert twins among them), "tail" (those of the p12 with a tail), "p13", "bytes", "raw_share" (the largest share of raw rows
         among the twins), "exception_share" (P12 exceptions over the P12 twins' weights)}."""
         from ..ops import wpack
 
-        if self.cfg.is_moe:
-            raise ValueError("packed weights: dense models only")
         st = {"tensors": 0, "packed": 0, "p12": 0, "tail": 0, "p13": 0, "bytes": 0, "raw_share": 0.0,
               "exception_share": 0.0}
         exc = w12 = 0

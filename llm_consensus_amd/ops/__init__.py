@@ -748,12 +748,27 @@ def gather_rows(x: torch.Tensor, rows: torch.Tensor, div: int, out: Optional[tor
     return out
 
 
-def moe_gemv(x, W_experts, ids, x_div, out, N, K, epi, norm_w=None, eps: float = 1e-5):
+def _use_packed_experts(Wp, tokens: int, W_experts, N: int, K: int) -> bool:
+    # the expert twin (wpack.PackedExperts12) of this very stack, for the rows the dense packed stream serves
+    return (Wp is not None and tokens <= GEMV_PACKED_MAX_M and isinstance(Wp, wpack.PackedExperts12)
+            and (Wp.E, Wp.rows, Wp.K) == (W_experts.shape[0], N, K) and tuple(W_experts.shape[1:]) == (N, K))
+
+
+def moe_gemv(x, W_experts, ids, x_div, out, N, K, epi, norm_w=None, eps: float = 1e-5,
+             Wp: Optional["wpack.PackedExperts12"] = None):
     """Decode expert GEMV over (token, slot) pairs; ``norm_w``: RMS-normalise x (raw hidden rows)
-    in the prologue."""
+    in the prologue. ``Wp``: the 12-bit twin of ``W_experts`` (``wpack.pack12_experts``); the pairs of 1-2
+    tokens then stream it instead (fewer bytes, the same output bits). A geometry or epilogue without a
+    packed kernel launches the bf16 one."""
     npairs = ids.numel()
-    kernels().moe_gemv(npairs, _p(x), x.stride(0), _p(norm_w) if norm_w is not None else 0, float(eps),
-                       _p(W_experts), _p(ids), x_div, _p(out), out.stride(0), N, K, epi, _s(x))
+    nw = _p(norm_w) if norm_w is not None else 0
+    tokens = ids.shape[0] if ids.dim() == 2 else -(-npairs // x_div)  # ids [tokens, k], or one x row per x_div pairs
+    if _use_packed_experts(Wp, tokens, W_experts, N, K):
+        if kernels().moe_gemv_p12(npairs, _p(x), x.stride(0), nw, float(eps), _p(W_experts), _p(Wp.planes), _p(Wp.hdr),
+                                  _p(ids), x_div, _p(out), out.stride(0), N, K, epi, _s(x)):
+            return out
+    kernels().moe_gemv(npairs, _p(x), x.stride(0), nw, float(eps), _p(W_experts), _p(ids), x_div, _p(out),
+                       out.stride(0), N, K, epi, _s(x))
     return out
 
 
@@ -771,10 +786,15 @@ def moe_gemvm(x, W_experts, ids, x_div, out, N, K, epi, norm_w=None, eps: float 
     return out
 
 
-def moe_down_combine(act, W_down, ids, w, h, N, K):
+def moe_down_combine(act, W_down, ids, w, h, N, K, Wp: Optional["wpack.PackedExperts12"] = None):
     """Decode MoE down projection fused with the combine (top-2): h[t] += sum_j w[t, j] *
-    (W_down[ids[t, j]] . act[t*2 + j]), fixed order, f32."""
+    (W_down[ids[t, j]] . act[t*2 + j]), fixed order, f32. ``Wp``: the 12-bit twin of ``W_down`` (as
+    ``moe_gemv``)."""
     T, k = ids.shape
+    if _use_packed_experts(Wp, T, W_down, N, K):
+        if kernels().moe_down_combine_p12(T, _p(act), act.stride(0), _p(W_down), _p(Wp.planes), _p(Wp.hdr), _p(ids),
+                                          _p(w), _p(h), h.stride(0), N, K, k, _s(act)):
+            return h
     kernels().moe_down_combine(T, _p(act), act.stride(0), _p(W_down), _p(ids), _p(w), _p(h), h.stride(0), N, K, k,
                                _s(act))
     return h

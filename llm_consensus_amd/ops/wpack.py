@@ -431,6 +431,45 @@ def pack12_tail(W: torch.Tensor) -> PackedWeight12Tail:
     return PackedWeight12Tail(planes, hdr, raw_rows, exceptions, N, K)
 
 
+# ---- P12 of a MoE expert stack ----
+#
+# A contiguous ``[E, N, K]`` stack is packed as its ``[E * N, K]`` view: rows are packed one by one, so
+# the planes and the records are the per-expert twins concatenated, and row n of expert e is row
+# ``e * N + n``, which is how the expert GEMVs index it. Whole 2048-weight units only (no tail, no P13).
+
+
+class PackedExperts12(PackedWeight12):
+    """The 12-bit twin of a bf16 ``[E, N, K]`` expert stack: a ``PackedWeight12`` over its ``[E * N, K]``
+    view (``N`` is E * N there), with ``E`` and ``rows``, the rows of one expert."""
+
+    __slots__ = ("E", "rows")
+
+    def __init__(self, pw: PackedWeight12, E: int):
+        super().__init__(pw.planes, pw.hdr, pw.raw_rows, pw.exceptions, pw.N, pw.K)
+        self.E, self.rows = E, pw.N // E
+
+
+# Expert launches on which the packed stream, cold and alone, was not faster than bf16 by more than the spread
+# of the two runs would be listed here as TAIL_STAYS_BF16 lists the tail shapes, (N, K) of one expert
+# (profiles/r12_packed_experts.md section 3); ``pack_best`` builds no twin for them.
+EXPERTS_STAY_BF16: dict = {}
+
+
+def expert_twin_wanted(N: int, K: int) -> bool:
+    """An expert shape ``[*, N, K]`` that ``pack_best`` packs."""
+    return packable12_shape(N, K) and (N, K) not in EXPERTS_STAY_BF16
+
+
+def pack12_experts(W: torch.Tensor) -> PackedExperts12:
+    """P12-pack a contiguous bf16 ``[E, N, K]`` expert stack where it lives (``pack12`` of its ``[E * N, K]``
+    view)."""
+    if W.dim() != 3 or W.dtype != torch.bfloat16 or not W.is_contiguous() or not packable12_shape(*W.shape[1:]):
+        raise ValueError(f"wpack12 experts: a contiguous bf16 [E, N, K] with K a multiple of {UNIT_ELEMS} up to "
+                         f"{MAX_K12}, got {W.dtype} {tuple(W.shape)}")
+    E, N, K = W.shape
+    return PackedExperts12(pack12(W.view(E * N, K)), E)
+
+
 def packed_format() -> int:
     """12 or 13: the format ``pack_best`` tries first (``LLMC_PACKED_FORMAT``, A/B runs)."""
     from ..parallel.placement import packed_format as fmt
@@ -442,7 +481,14 @@ def pack_best(W: torch.Tensor, fmt: Optional[int] = None):
     """The P12 twin of ``W``; where more than MAX_RAW_SHARE of its rows would be raw (or the shape
     is off P12's), the P13 twin; where that fails too, None. ``fmt`` 13 skips P12. A K off the
     2048-weight unit has the 12-bit format with a tail only (``tail_twin_wanted``: a tail shape that did
-    not measure slower than bf16): that twin, or None where too many rows are raw or ``fmt`` is 13."""
+    not measure slower than bf16): that twin, or None where too many rows are raw or ``fmt`` is 13.
+    A 3-D ``[E, N, K]`` expert stack has the 12-bit format on whole units only: ``pack12_experts``' twin, or
+    None likewise."""
+    if W.dim() == 3:
+        if (packed_format() if fmt is None else fmt) != 12 or not expert_twin_wanted(*W.shape[1:]):
+            return None
+        pwe = pack12_experts(W.contiguous())
+        return pwe if pwe.raw_share <= MAX_RAW_SHARE else None
     if W.dim() != 2:
         return None
     if not packable_shape(*W.shape):

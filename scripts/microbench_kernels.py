@@ -269,6 +269,52 @@ def bench_packed(model="llama-3-8b", rows=(1,), only=None):
         torch.cuda.empty_cache()
 
 
+def bench_packed_experts(E=8, H=4096, I=14336, tokens=(1,)):
+    """Mixtral's decode expert launches on the 12-bit twin of the expert stack against the bf16 stream, on
+    COLD weights: gate_up (norm prologue, SiLU epilogue; N = 2 I, K = H) and down + combine (N = H, K = I),
+    top-2. One launch streams two experts (470 / 235 MB); the graph cycles through the E / 2 disjoint expert
+    pairs of one stack, 1.9 GB, so every launch reads weights the 256 MB MALL no longer holds. Each form is
+    timed twice, alternating: the spread between the runs is the noise floor."""
+    from llm_consensus_amd.ops import wpack
+
+    for name, N, K in (("gate_up", 2 * I, H), ("down+combine", H, I)):
+        W = torch.empty(E, N, K, dtype=BF, device="cuda")
+        for e in range(E):
+            W[e] = (torch.randn(N, K, device="cuda") * K ** -0.5).to(BF)
+        torch.cuda.synchronize()
+        P = wpack.pack12_experts(W)
+        for T in tokens:
+            pairs = [torch.tensor([[(2 * (j + t)) % E, (2 * (j + t) + 1) % E] for t in range(T)], dtype=torch.int32,
+                                  device="cuda") for j in range(E // 2)]
+            if name == "gate_up":
+                x = torch.randn(T, K, device="cuda").to(BF)
+                nw = torch.ones(K, dtype=BF, device="cuda")
+                out = torch.zeros(2 * T, N // 2, dtype=BF, device="cuda")
+
+                def run(twin):
+                    for ids in pairs:
+                        ops.moe_gemv(x, W, ids, 2, out, N, K, 3, norm_w=nw, Wp=twin)
+            else:
+                x = torch.randn(2 * T, K, device="cuda").to(BF)
+                w = torch.full((T, 2), 0.5, device="cuda")
+                h = torch.zeros(T, N, dtype=BF, device="cuda")
+
+                def run(twin):
+                    for ids in pairs:
+                        ops.moe_down_combine(x, W, ids, w, h, N, K, Wp=twin)
+            res = []
+            for _ in range(2):
+                res.append(tuple(round(timeit(lambda: run(t), iters=4, warm=1) / len(pairs), 3) for t in (None, P)))
+            b, q = (min(r[i] for r in res) for i in range(2))
+            spread = max(abs(res[0][i] - res[1][i]) / min(res[0][i], res[1][i]) for i in range(2))
+            gb = 2 * T * N * K * 2 / 1e3
+            print(f"packed-experts {name:12s} E={E} N={N:6d} K={K:5d} T={T}: bf16 {b:7.2f} us ({gb / b / 1e3:5.2f} TB/s)  "
+                  f"p12 {q:7.2f} us ({gb * 0.75 / q / 1e3:5.2f} TB/s) ratio {q / b:.3f} (spread {100 * spread:.1f} %)  "
+                  f"raw rows {P.raw_rows} of {E * N}, exceptions {P.exceptions}  runs {res}", flush=True)
+        del W, P
+        torch.cuda.empty_cache()
+
+
 SWEEP = ["256x1u8", "256x2u4", "256x4u4", "512x1u8", "512x2u4", "128x1u8", "64x1u8", "1024x1u4", "256x1u4",
          "256x2u8", "512x4u2", "128x2u4", "1024x1u8", "1024x2u4", "1024x2u2", "1024x1u2", "768x1u4", "1024x4u2", "1024x1u6",
          "768x2u4", "640x1u8", "896x1u4", "768x2u2", "1024x2u2b"]
@@ -598,6 +644,8 @@ if __name__ == "__main__":
         bench_packed(model=argv[argv.index("--model") + 1] if "--model" in argv else "llama-3-8b",
                      rows=(1, 2) if "--rows2" in argv else (1,),
                      only=argv[argv.index("--only") + 1].split(",") if "--only" in argv else None)
+    if what in ("packed-experts",):  # Mixtral's expert launches from the 12-bit twin of the stack
+        bench_packed_experts(tokens=(1, 2) if "--rows2" in argv else (1,))
     if what in ("sweep-phi3",):  # Phi-3-mini shapes (K = 3072 / 8192)
         bench_gemv_sweep([(9216, 3072), (16384, 3072), (3072, 3072), (3072, 8192)])
     if what in ("sweep-tp8",):  # one TP=8 rank of Llama-3-8B: qkv, gate_up, o, down
