@@ -108,6 +108,8 @@ int llmc_car_reset(void*, size_t);
 size_t llmc_car_oneshot_max(size_t);
 int llmc_gemv_ar(int, const void*, int, const void*, void*, int, int, int, const void* const*, void*, int, int, size_t,
                  hipStream_t);
+int llmc_gemv_ar_p12(int, const void*, int, const void*, const void*, const void*, void*, int, int, int,
+                     const void* const*, void*, int, int, size_t, hipStream_t);
 int llmc_stream_cu_mask(int, const uint32_t*, int, void**);
 int llmc_can_access_peer(int, int, int*);
 int llmc_car_twoshot(const void* const*, void*, int, int, size_t, int, const void*, void*, long, int, int, hipStream_t);
@@ -403,6 +405,16 @@ PYBIND11_MODULE(_llmc_hip, m) {
     std::vector<const void*> b(bases.size());
     for (size_t i = 0; i < bases.size(); ++i) b[i] = P(bases[i]);
     check(llmc_gemv_ar(M, P(x), xs, P(W), P(h), hs, N, K, b.data(), P(host), rank, world, cap, S(s)), "gemv_ar");
+  });
+  // from W's 12-bit twin: true = launched; false = no packed kernel for this geometry, nothing launched
+  m.def("gemv_ar_p12", [](int M, ptr x, int xs, ptr W, ptr planes, ptr recs, ptr h, int hs, int N, int K,
+                          const std::vector<ptr>& bases, ptr host, int rank, int world, size_t cap, ptr s) {
+    std::vector<const void*> b(bases.size());
+    for (size_t i = 0; i < bases.size(); ++i) b[i] = P(bases[i]);
+    const int rc = llmc_gemv_ar_p12(M, P(x), xs, P(W), P(planes), P(recs), P(h), hs, N, K, b.data(), P(host), rank,
+                                    world, cap, S(s));
+    if (rc != -8) check(rc, "gemv_ar_p12");
+    return rc == 0;
   });
   // a stream restricted to a set of CUs (rehearsals: ranks sharing one GPU on disjoint CUs)
   m.def("stream_cu_mask", [](int device, const std::vector<uint32_t>& mask) {

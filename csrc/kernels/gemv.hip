@@ -267,8 +267,10 @@ extern "C" int llmc_gemv_qkv_rope_p12(int M, const void* x, int x_stride, const 
 namespace llmc {
 template <int M, int NT, int UNROLL>
 static int launch_gemv_ar(const void* x, int x_stride, const void* W, void* h, int h_stride, int N, int K,
-                          const CarArgs& ar, hipStream_t s) {
+                          const CarArgs& ar, const PackedW& pw, hipStream_t s) {
   constexpr int WAVES = NT / kWave;
+  if (pw.planes != nullptr)  // the chosen geometry as data: gemv_ar_p12.hip holds the packed EPI_AR kernels
+    return launch_gemv_ar_p12(M, NT, UNROLL, x, x_stride, W, pw, h, h_stride, N, K, ar, s);
   auto kern = gemv_kernel<M, NT, 1, UNROLL, PRO_NONE, EPI_AR, false>;
   const size_t lds = static_cast<size_t>(M) * K * sizeof(bf16_t) + 2 * M * WAVES * sizeof(float);
   if (lds > 160 * 1024) return -2;
@@ -288,24 +290,26 @@ static int launch_gemv_ar(const void* x, int x_stride, const void* W, void* h, i
 
 template <int M>
 static int gemv_ar_geom(const void* x, int x_stride, const void* W, void* h, int h_stride, int N, int K,
-                        const CarArgs& ar, hipStream_t s) {
+                        const CarArgs& ar, const PackedW& pw, hipStream_t s) {
   // the dense GEMV's geometry rule (pick_waves): same blocks, same accumulation order, same bits
   const int w = pick_waves(N, false);
-  if (w == 16 && K >= 8192 && N <= 4096) return launch_gemv_ar<M, 1024, 8>(x, x_stride, W, h, h_stride, N, K, ar, s);
-  if (w == 10 && K >= 8192) return launch_gemv_ar<M, 640, 8>(x, x_stride, W, h, h_stride, N, K, ar, s);
+  if (w == 16 && K >= 8192 && N <= 4096) return launch_gemv_ar<M, 1024, 8>(x, x_stride, W, h, h_stride, N, K, ar, pw, s);
+  if (w == 10 && K >= 8192) return launch_gemv_ar<M, 640, 8>(x, x_stride, W, h, h_stride, N, K, ar, pw, s);
   switch (w) {
-    case 16: return launch_gemv_ar<M, 1024, 4>(x, x_stride, W, h, h_stride, N, K, ar, s);
-    case 12: return launch_gemv_ar<M, 768, 4>(x, x_stride, W, h, h_stride, N, K, ar, s);
-    case 10: return launch_gemv_ar<M, 640, 4>(x, x_stride, W, h, h_stride, N, K, ar, s);
-    case 8: return launch_gemv_ar<M, 512, 4>(x, x_stride, W, h, h_stride, N, K, ar, s);
-    case 4: return launch_gemv_ar<M, 256, 8>(x, x_stride, W, h, h_stride, N, K, ar, s);
+    case 16: return launch_gemv_ar<M, 1024, 4>(x, x_stride, W, h, h_stride, N, K, ar, pw, s);
+    case 12: return launch_gemv_ar<M, 768, 4>(x, x_stride, W, h, h_stride, N, K, ar, pw, s);
+    case 10: return launch_gemv_ar<M, 640, 4>(x, x_stride, W, h, h_stride, N, K, ar, pw, s);
+    case 8: return launch_gemv_ar<M, 512, 4>(x, x_stride, W, h, h_stride, N, K, ar, pw, s);
+    case 4: return launch_gemv_ar<M, 256, 8>(x, x_stride, W, h, h_stride, N, K, ar, pw, s);
     default: return -7;
   }
 }
 }  // namespace llmc
 
-extern "C" int llmc_gemv_ar(int M, const void* x, int x_stride, const void* W, void* h, int h_stride, int N, int K,
-                            const void* const* bases, void* host, int rank, int world, size_t cap, hipStream_t s) {
+namespace llmc {
+static int gemv_ar_entry(int M, const void* x, int x_stride, const void* W, void* h, int h_stride, int N, int K,
+                         const void* const* bases, void* host, int rank, int world, size_t cap, const PackedW& pw,
+                         hipStream_t s) {
   if (K % 8 != 0 || N % 2 != 0 || world < 1 || world > kMaxRanks || rank < 0 || rank >= world) return -1;
   CarArgs ar{};
   for (int r = 0; r < kMaxRanks; ++r)
@@ -315,10 +319,30 @@ extern "C" int llmc_gemv_ar(int M, const void* x, int x_stride, const void* W, v
   ar.world = world;
   ar.cap = static_cast<long>(cap);
   switch (M) {
-    case 1: return gemv_ar_geom<1>(x, x_stride, W, h, h_stride, N, K, ar, s);
-    case 2: return gemv_ar_geom<2>(x, x_stride, W, h, h_stride, N, K, ar, s);
+    case 1: return gemv_ar_geom<1>(x, x_stride, W, h, h_stride, N, K, ar, pw, s);
+    case 2: return gemv_ar_geom<2>(x, x_stride, W, h, h_stride, N, K, ar, pw, s);
     default: return -3;
   }
+}
+}  // namespace llmc
+
+extern "C" int llmc_gemv_ar(int M, const void* x, int x_stride, const void* W, void* h, int h_stride, int N, int K,
+                            const void* const* bases, void* host, int rank, int world, size_t cap, hipStream_t s) {
+  return gemv_ar_entry(M, x, x_stride, W, h, h_stride, N, K, bases, host, rank, world, cap, PackedW{}, s);
+}
+
+// llmc_gemv_ar with W_r streamed from its 12-bit planes and row records (`planes`, `recs`: wpack.hip, the P12
+// layout, with the row tail where K is off the 2048-weight unit; W is read for raw rows). Same geometry, same
+// blocks and granules, same bits as llmc_gemv_ar, so a rank may run this beside peers that run the bf16 launch.
+// -8: no packed kernel for this geometry, nothing was launched (the caller launches llmc_gemv_ar).
+extern "C" int llmc_gemv_ar_p12(int M, const void* x, int x_stride, const void* W, const void* planes, const void* recs,
+                                void* h, int h_stride, int N, int K, const void* const* bases, void* host, int rank,
+                                int world, size_t cap, hipStream_t s) {
+  if (M < 1 || M > kGemvMaxM || K % kP12ChunkElems != 0 || K < kP13UnitElems || K > kP12MaxK || planes == nullptr ||
+      recs == nullptr || reinterpret_cast<uintptr_t>(recs) % 4 != 0)
+    return -1;
+  const PackedW pw{static_cast<const uint8_t*>(planes), static_cast<const uint8_t*>(recs), WF_P12};
+  return gemv_ar_entry(M, x, x_stride, W, h, h_stride, N, K, bases, host, rank, world, cap, pw, s);
 }
 
 // MoE decode (K11 at batch 1): one GEMV per (token, top-k slot) pair against the selected

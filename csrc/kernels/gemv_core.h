@@ -130,6 +130,11 @@ int launch_moe_gemv_p12(int NT, int RPW, int pro, int epi, int npairs, const voi
                         int out_stride, int N, int K, hipStream_t s);
 int launch_moe_combine_p12(int T, const void* act, int act_stride, const void* W, const PackedW& pw, const void* ids,
                            const void* w, void* h, int h_stride, int N, int K, hipStream_t s);
+// The WF_P12 launch of the row-parallel GEMV with the fused all-reduce (EPI_AR; gemv_ar_p12.hip) in the
+// geometry (NT, UNROLL) that gemv.hip's gemv_ar_geom chose. -8: not instantiated (the caller launches the
+// bf16 kernel: the same bits).
+int launch_gemv_ar_p12(int M, int NT, int UNROLL, const void* x, int x_stride, const void* W, const PackedW& pw, void* h,
+                       int h_stride, int N, int K, const CarArgs& ar, hipStream_t s);
 struct P12Unit {  // 12 dwords for 32 weights
   u32x4 l0, l1, n;
 };
@@ -187,7 +192,9 @@ __device__ __forceinline__ void gemv_block(const int bx, const int by, char* sme
   constexpr int kUnitBytes = P12 ? kP12UnitBytes : kP13UnitBytes;
   static_assert(DEPTH == 1 || (DEPTH == 2 && P13), "prefetch depth: the packed loop, 1 or 2 batches ahead");
   static_assert(!TAIL || (P12 && DEPTH == 1), "a tail: the 12-bit format, one batch ahead");
-  static_assert(!P13 || (EPI != EPI_AR && UNROLL % 4 == 0 && M <= 2), "packed weights: the one- and two-row decode forms");
+  static_assert(!P13 || (UNROLL % 4 == 0 && M <= 2), "packed weights: the one- and two-row decode forms");
+  // EPI_AR streams the 12-bit planes only (gemv_ar_p12.hip), one row per wave, one batch ahead; no 13-bit form
+  static_assert(!P13 || EPI != EPI_AR || (P12 && RPW == 1 && DEPTH == 1), "packed EPI_AR: 12 bits, one batch ahead");
   // MoE experts (pair form and EPI_COMBINE): the 12-bit twin of the [E * N, K] view of the expert stack, whole
   // units only, one unit per batch (the only unroll the MoE launchers use)
   static_assert(!P13 || !EXPERT || (P12 && !TAIL && DEPTH == 1 && UNROLL == 4),

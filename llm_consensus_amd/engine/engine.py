@@ -96,7 +96,8 @@ class EngineConfig:
     fused_ar: bool = True
     # decode GEMVs of 1-2 rows stream a lossless 13-bit packed twin of their weights (ops.wpack:
     # 0.8125 of the bytes, the same output bits) built beside the bf16 tensors at engine build.
-    # "auto": TP = 1 on the GPU with max_batch <= 2 (a MoE model's expert stacks included), when the twin fits in the free
+    # "auto": on the GPU with max_batch <= 2 (a TP rank of a dense model: its own shards; a MoE model, TP = 1 only:
+    # its expert stacks included), when the twin fits in the free
     # device memory with PACKED_MARGIN_BYTES to spare; "on": the same without the memory check;
     # "off". Environment default (A/B runs): LLMC_PACKED_WEIGHTS.
     packed_weights: str = dataclasses.field(default_factory=packed_weights_mode)
@@ -300,8 +301,17 @@ class Engine:
 
     def _build_packed_weights(self) -> None:
         """The packed decode twins of the weights (``EngineConfig.packed_weights``), with a log line
-        either way. The o_proj twin is skipped where every bucket runs the fused attention + o_proj
-        launch, which reads the bf16 ``w_o``."""
+        either way. Twins nobody reads are not built: the o_proj twin is skipped where every bucket runs
+        the fused attention + o_proj launch, which reads the bf16 ``w_o``, and the qkv twin on a one-row
+        engine whose every bucket runs the one-launch qkv + attention, which projects from bf16.
+
+        A TP rank of a dense model packs its own shards; a shard shape the formats do not take (K under
+        2048 or no multiple of 512) has no twin and streams bf16. The packed launches, the row-parallel one
+        with the all-reduce in its epilogue included, return the bits of the bf16 launches in the same
+        geometry, so the ranks of a group need not agree: a rank whose twin does not fit in its free memory,
+        or whose tensor has more than 1 % raw rows, streams bf16 beside packed peers, and that is what
+        makes the "auto" rule safe rank by rank. MoE models under TP or expert parallelism stay off: their
+        expert shards would need an expert tail, and the EP paths have not run with twins."""
         mode = str(self.ecfg.packed_weights).lower()
         self.packed = False
         if mode not in ("auto", "on", "off"):
@@ -311,25 +321,32 @@ class Engine:
             why = "switched off"
         elif not self.on_gpu:
             why = "not on a GPU"
-        elif self.tp.size != 1:  # hence no expert parallelism either
-            why = "TP = 1 only"
+        elif self.tp.size != 1 and self.cfg.is_moe:  # hence expert parallelism too
+            why = "a MoE model's expert shards under TP / expert parallelism have no packed form"
         elif self.ecfg.max_batch > ops.GEMV_PACKED_MAX_M:
             why = f"max_batch {self.ecfg.max_batch} decodes on the MFMA form"
         if why is None and self.w.p_lm_head is None and not any(L.p_qkv or L.p_gu or L.p_down for L in self.w.layers):
-            with_o = not (self.ecfg.max_batch == 1 and all(self.ao_chunks))
-            need = self.w.packed_demand(with_o)
+            one_row = self.ecfg.max_batch == 1
+            with_o = not (one_row and all(self.ao_chunks))
+            with_qkv = not (one_row and all(self.qa_plan))
+            # the shard shapes that stay bf16 in the fused all-reduce launch (ops.wpack.AR_STAYS_BF16)
+            fused = self.tp.size > 1 and self.ecfg.fused_ar and self.tp.custom_fused is not None
+            fused = self.ecfg.max_batch if fused else 0  # the engine's decode rows under the fused launch
+            need = self.w.packed_demand(with_o, with_qkv, fused)
             free = torch.cuda.mem_get_info(self.device)[0]
             if need == 0:
                 why = "no weight the packed formats take (K a multiple of 2048; at 12 bits, of 512 above 2048)"
             elif mode == "auto" and need + PACKED_MARGIN_BYTES > free:
                 why = f"the twin ({need / 2**30:.2f} GiB) does not fit in {free / 2**30:.2f} GiB free"
             else:
-                st = self.w.pack_decode_weights(with_o)
-                log.info("%s: packed weights on: %d of %d tensors (%d at 12 bits, %d of them with a row tail, %d at 13), "
+                st = self.w.pack_decode_weights(with_o, with_qkv, fused)
+                whose = f" (TP rank {self.tp.rank} of {self.tp.size}: its own shards)" if self.tp.size > 1 else ""
+                log.info("%s: packed weights on%s: %d of %d tensors (%d at 12 bits, %d of them with a row tail, %d at 13), "
                          "%.2f GiB beside %.2f GiB "
                          "bf16, exceptions %.4f %% of the 12-bit weights, raw rows <= %.3f %%",
-                         self.name, st["packed"], st["tensors"], st["p12"], st["tail"], st["p13"], st["bytes"] / 2**30,
-                         self.w.nbytes() / 2**30, 100 * st["exception_share"], 100 * st["raw_share"])
+                         self.name, whose, st["packed"], st["tensors"], st["p12"], st["tail"], st["p13"],
+                         st["bytes"] / 2**30, self.w.nbytes() / 2**30, 100 * st["exception_share"],
+                         100 * st["raw_share"])
         if why is not None:
             log.info("%s: packed weights off: %s", self.name, why)
             return
@@ -620,7 +637,7 @@ class Engine:
         GEMV's epilogue (EPI_AR); otherwise the GEMV/GEMM, then the group's all-reduce."""
         car = self.tp.custom_fused if self.ecfg.fused_ar else None
         if car is not None and h.is_cuda and x.shape[0] <= 2 and not self.mfma_decode and h.is_contiguous():
-            car.gemv_allreduce(x, W, h)
+            car.gemv_allreduce(x, W, h, Wp)
             return
         ops.linear(x, W, EPI_RESADD if self.tp.rank == 0 else EPI_BF16, out=h, mfma=self.mfma_decode, Wp=Wp)
         self.tp.all_reduce_(h)
@@ -739,7 +756,7 @@ class Engine:
         qa = self.qa_plan[bi] if B == 1 else None
         dbg = self._debug_layer_io  # eager debug steps only: each layer's input, then the last output
         layers = self.w.layers
-        pk = self.packed  # the 13-bit packed twins where the weights have them (TP = 1, <= 2 rows)
+        pk = self.packed  # the packed twins where the weights (a TP rank: its shards) have them (<= 2 rows)
         for li, Lw in enumerate(layers):
             if dbg is not None:
                 dbg.append(h.clone())
@@ -754,7 +771,7 @@ class Engine:
                              self.scale, fault=self.attn_fault, w_o=Lw.w_o if o_in else None, h=h if o_in else None,
                              add_resid=tp.rank == 0, car=car)
                 if not o_in:
-                    self._row_parallel(attn, Lw.w_o, h)
+                    self._row_parallel(attn, Lw.w_o, h, Lw.p_o if pk else None)
                 elif tp.size > 1 and car is None:
                     tp.all_reduce_(h)
             else:

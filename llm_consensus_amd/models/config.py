@@ -83,8 +83,13 @@ class ModelConfig:
     def weight_bytes(self, dtype_bytes: int = 2) -> int:
         return self.num_params() * dtype_bytes
 
-    def packed_twin_bytes(self) -> int:
-        """Bytes of the 13-bit packed decode twins (ops.wpack) an unsharded dense engine builds beside
+    def packed_twin_bytes(self, tp: int = 1) -> int:
+        """Bytes of the packed decode twins ONE rank of a ``tp``-way engine builds beside its bf16 shards
+        (``tp`` = 1, the default: the unsharded engine): the shapes below with the column-parallel outputs
+        (qkv, gate_up), the row-parallel inputs (o_proj, down) and the vocabulary divided by ``tp``. A shard
+        shape no format takes (K under 2048 or no multiple of 512) counts nothing; a MoE model has twins at
+        ``tp`` = 1 only (0 above). Per shape:
+        the bytes of the 13-bit packed decode twins (ops.wpack) an unsharded dense engine builds beside
         its bf16 weights: 13/16 of every decode GEMV weight whose K is a whole number of 2048-weight
         units (the o_proj twin counted too: the upper bound), and the 12-bit twin with a row tail
         (12/16 and a 68-byte record per row) of every one whose K is another multiple of 512 above
@@ -92,6 +97,8 @@ class ModelConfig:
         dense parts as above (the router has no twin) and the 12-bit twin of each expert stack whose K is a whole
         number of units (12/16 and a 68-byte record per row; no tail, so nothing for another K)."""
         h, i = self.hidden, self.intermediate
+        if tp != 1 and self.is_moe:
+            return 0
 
         def twin(n: int, k: int) -> int:
             if k % 2048 == 0:
@@ -102,9 +109,9 @@ class ModelConfig:
             rows = self.n_experts * n
             return rows * k * 12 // 8 + 68 * rows if k % 2048 == 0 and k <= 65536 - 2048 else 0
 
-        shapes = [(self.qkv_size, h), (h, self.q_size)]
-        ffn = experts(2 * i, h) + experts(h, i) if self.is_moe else twin(2 * i, h) + twin(h, i)
-        return self.n_layers * (sum(twin(n, k) for n, k in shapes) + ffn) + twin(self.vocab, h)
+        shapes = [(self.qkv_size // tp, h), (h, self.q_size // tp)]
+        ffn = experts(2 * i, h) + experts(h, i) if self.is_moe else twin(2 * i // tp, h) + twin(h, i // tp)
+        return self.n_layers * (sum(twin(n, k) for n, k in shapes) + ffn) + twin(self.vocab // tp, h)
 
     def kv_bytes_per_token(self, dtype_bytes: int = 2) -> int:
         return 2 * self.n_layers * self.kv_size * dtype_bytes

@@ -185,15 +185,17 @@ class TransformerWeights:
         return self
 
     # -- packed decode twins ---------------------------------------------------------------------
-    def packed_demand(self, with_o: bool = True) -> int:
-        """Bytes ``pack_decode_weights`` would allocate (a tensor with K off the 2048-weight unit counts
-        its 12-bit twin with a tail where it has one, else nothing; a MoE layer's expert stacks their 12-bit
-        twins on whole units, the router nothing)."""
+    def packed_demand(self, with_o: bool = True, with_qkv: bool = True, fused_ar_rows: int = 0) -> int:
+        """Bytes ``pack_decode_weights`` would allocate for this rank's tensors (a tensor with K off the
+        2048-weight unit counts its 12-bit twin with a tail where it has one, else nothing; a MoE layer's
+        expert stacks their 12-bit twins on whole units, the router nothing)."""
         from ..ops import wpack
 
         ts = [self.lm_head]
         for L in self.layers:
-            ts += [L.w_qkv, L.w_gu, L.w_down] + ([L.w_o] if with_o else [])
+            ts += [L.w_gu] + ([L.w_qkv] if with_qkv else [])
+            ts += [W for W in [L.w_down] + ([L.w_o] if with_o else [])
+                   if not (fused_ar_rows and W.dim() == 2 and not wpack.ar_twin_wanted(*W.shape, fused_ar_rows))]
         fmt = wpack.packed_format()
 
         def size(N, K):
@@ -206,8 +208,11 @@ class TransformerWeights:
 
         return sum(size(*t.shape) if t.dim() == 2 else experts(*t.shape) for t in ts if t.dim() in (2, 3))
 
-    def pack_decode_weights(self, with_o: bool = True) -> dict:
-        """Build the packed twins of the decode GEMVs' weights (``ops.wpack.pack_best``: 12-bit, else
+    def pack_decode_weights(self, with_o: bool = True, with_qkv: bool = True, fused_ar_rows: int = 0) -> dict:
+        """Build the packed twins of the decode GEMVs' weights, a TP rank's of its own shards
+        (``with_o`` / ``with_qkv`` False: no o_proj / qkv twin, which no launch of the engine would read;
+        ``fused_ar_rows`` > 0: the row-parallel tensors run the launch with the all-reduce in its epilogue on
+        an engine of that many decode rows, and the shapes ``ops.wpack.AR_STAYS_BF16`` lists for it get no twin) (``ops.wpack.pack_best``: 12-bit, else
         13-bit; 12-bit with a tail for a K off the 2048-weight unit; a MoE layer's expert stacks ``w_gu`` /
         ``w_down`` at 12 bits on whole units, its router stays bf16) beside the bf16 tensors, which stay
         (prefill and raw rows read them). A tensor no format takes, or with more than 1 % raw rows in
@@ -223,7 +228,7 @@ class TransformerWeights:
         def twin(W):
             nonlocal exc, w12
             st["tensors"] += 1
-            pw = wpack.pack_best(W)
+            pw = wpack.pack_best(W if W.is_contiguous() else W.contiguous())
             if pw is not None:
                 st["packed"] += 1
                 st["bytes"] += pw.nbytes()
@@ -239,8 +244,13 @@ class TransformerWeights:
 
         self.p_lm_head = twin(self.lm_head)
         for L in self.layers:
-            L.p_qkv, L.p_gu, L.p_down = twin(L.w_qkv), twin(L.w_gu), twin(L.w_down)
-            L.p_o = twin(L.w_o) if with_o else None
+            def row_parallel(W):
+                keep = not fused_ar_rows or W.dim() != 2 or wpack.ar_twin_wanted(*W.shape, fused_ar_rows)
+                return twin(W) if keep else None
+
+            L.p_qkv = twin(L.w_qkv) if with_qkv else None
+            L.p_gu, L.p_down = twin(L.w_gu), row_parallel(L.w_down)
+            L.p_o = row_parallel(L.w_o) if with_o else None
         st["exception_share"] = exc / max(1, w12)
         return st
 

@@ -350,6 +350,27 @@ def tail_twin_wanted(N: int, K: int) -> bool:
     return packable12_tail_shape(N, K) and (N, K) not in TAIL_STAYS_BF16
 
 
+# The same choice for a TP rank's row-parallel shards (o_proj, down_proj) in the launch with the all-reduce
+# in its epilogue (csrc/kernels/gemv_ar_p12.hip): shard shapes on which the packed launch, cold, two ranks
+# each on half of the CUs (scripts/ar_packed_launch.py; profiles/r13_packed_tp.md section 3), was not
+# faster than the bf16 launch by more than the spread of the runs. Such a shard gets no twin on an engine
+# that runs the fused launch with that many decode rows; with separate all-reduce launches it is an
+# ordinary GEMV and the rules above apply.
+# (N, K): (fewest decode rows from which it stays bf16, packed / bf16 time at one row, at two rows)
+AR_STAYS_BF16 = {
+    (8192, 3584): (1, 1.051, 1.076),  # Llama-3-70B down on 8 ranks: 23.9 against 22.7 us
+    (4096, 3584): (1, 1.040, 1.032),  # Llama-3-8B down on 4 ranks: 14.1 against 13.5 us
+    (8192, 2048): (2, 0.952, 1.067),  # Llama-3-70B o_proj on 4 ranks: 15.0 against 15.8 us at one row, 17.8 against 16.6 at two
+    (4096, 2048): (2, 0.946, 1.042),  # Llama-3-8B o_proj on 2 ranks: 9.4 against 10.0 us, 11.1 against 10.7 at two
+}
+
+
+def ar_twin_wanted(N: int, K: int, rows: int = 1) -> bool:
+    """A row-parallel shard shape that keeps its twin under the fused all-reduce launch on an engine of
+    ``rows`` decode rows (``max_batch``)."""
+    return rows < AR_STAYS_BF16.get((N, K), (3,))[0]
+
+
 def _row_bytes12(K: int) -> int:
     return K // UNIT_ELEMS * UNIT12_BYTES + K % UNIT_ELEMS // CHUNK_ELEMS * TAIL_CHUNK_BYTES
 

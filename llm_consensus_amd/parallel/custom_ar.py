@@ -157,14 +157,29 @@ class CustomAllReduce:
         return nbytes % 16 == 0 and nbytes <= kernels().car_oneshot_max(self.cap)
 
     # -- fused into the row-parallel GEMV (decode o_proj / down_proj) -----------------------------
-    def gemv_allreduce(self, x: torch.Tensor, W: torch.Tensor, h: torch.Tensor) -> torch.Tensor:
+    def gemv_allreduce(self, x: torch.Tensor, W: torch.Tensor, h: torch.Tensor, Wp=None) -> torch.Tensor:
         """h = sum over ranks of W_r . x_r, rank 0's term + h (the residual): one GEMV launch with
         the one-shot exchange in its epilogue (gemv_core.h EPI_AR). x [M <= 2, K], W [N, K], h [M, N]
-        bf16; same bits as ``linear(EPI_RESADD / EPI_BF16)`` + ``all_reduce_``."""
+        bf16; same bits as ``linear(EPI_RESADD / EPI_BF16)`` + ``all_reduce_``.
+
+        ``Wp``: the 12-bit packed twin of this rank's ``W`` (``ops.wpack.PackedWeight12``, with a row
+        tail or without): the launch streams it instead of ``W`` (csrc/kernels/gemv_ar_p12.hip), in the
+        bf16 launch's geometry and with its bits, so the ranks of a group need not agree on it. A 13-bit
+        twin has no fused form and ``None`` is the bf16 stream: both are the launch above."""
+        from ..ops import wpack
+
         M, K = x.shape
         N = W.shape[0]
-        kernels().gemv_ar(M, x.data_ptr(), x.stride(0), W.data_ptr(), h.data_ptr(), h.stride(0), N, K, self.bases,
-                          self.host_dev, self.rank, self.world, self.cap, self._stream(h))
+        k = kernels()
+        if isinstance(Wp, wpack.PackedWeight12) and not isinstance(Wp, wpack.PackedExperts12) and M <= 2:
+            if (Wp.N, Wp.K) != (N, K):
+                raise ValueError(f"gemv_allreduce: packed twin of a [{Wp.N}, {Wp.K}] tensor for W [{N}, {K}]")
+            if k.gemv_ar_p12(M, x.data_ptr(), x.stride(0), W.data_ptr(), Wp.planes.data_ptr(), Wp.hdr.data_ptr(),
+                             h.data_ptr(), h.stride(0), N, K, self.bases, self.host_dev, self.rank, self.world, self.cap,
+                             self._stream(h)):
+                return h
+        k.gemv_ar(M, x.data_ptr(), x.stride(0), W.data_ptr(), h.data_ptr(), h.stride(0), N, K, self.bases,
+                  self.host_dev, self.rank, self.world, self.cap, self._stream(h))
         return h
 
     @staticmethod

@@ -68,6 +68,16 @@ def kv_pool_blocks(placement, specs, ctx: Dict[str, int], seqs: Dict[str, int],
     return out
 
 
+def model_demand(name: str, c, ctx_len: int, tp: int, is_judge: bool = False, on_cpu: bool = False) -> ModelDemand:
+    """The placement demand of one model on ``tp`` GPUs. A GPU engine also builds the packed decode twins
+    of its weights (EngineConfig.packed_weights, unless switched off): an unsharded engine those of its
+    tensors, every rank of a dense TP engine those of its own shards (a MoE model under TP builds none).
+    ``ModelDemand.weight_bytes`` is the model's over all its GPUs (the solver divides it by ``tp``), so the
+    twin is counted the same way: ``tp`` times one rank's ``ModelConfig.packed_twin_bytes(tp)``."""
+    twin = tp * c.packed_twin_bytes(tp) if (not on_cpu and packed_weights_mode() != "off") else 0
+    return ModelDemand(name, c.weight_bytes() + twin, c.kv_bytes_per_token() * ctx_len, tp, is_judge)
+
+
 class LocalError(Exception):
     pass
 
@@ -175,11 +185,7 @@ class LocalBackend:
                 tp = len(pins[s.name])
             else:
                 tp = 1 if force_cpu else min(c.default_tp, len(gpu_ids))
-            # an unsharded dense GPU engine also builds the packed decode twins of its weights
-            # (EngineConfig.packed_weights, unless switched off)
-            twin = c.packed_twin_bytes() if (tp == 1 and not force_cpu and packed_weights_mode() != "off") else 0
-            demands.append(ModelDemand(s.name, c.weight_bytes() + twin, c.kv_bytes_per_token() * ctx_len, tp,
-                                       s.name == judge))
+            demands.append(model_demand(s.name, c, ctx_len, tp, s.name == judge, force_cpu))
         if force_cpu and not pins:
             from ..parallel.placement import Placement
 
