@@ -43,7 +43,10 @@ struct Philox {
 
 __device__ __forceinline__ float gumbel(uint64_t key, uint32_t idx, uint32_t step) {
   const uint32_t r = Philox::draw(key, idx, step);
-  const float u = (static_cast<float>(r >> 8) + 0.5f) * (1.0f / 16777216.0f);  // (0,1)
+  // (0,1], not (0,1): 0xFFFFFF + 0.5 rounds up to 2^24 in float, so one draw in 2^24 gives u = 1 and
+  // g = +inf, and that index wins whatever its logit. Known, and pinned as it is by the sampler tests
+  // (SATURATED_DRAWS): capping u would change the tokens of every long sampled sequence.
+  const float u = (static_cast<float>(r >> 8) + 0.5f) * (1.0f / 16777216.0f);
   return -__logf(-__logf(u));
 }
 
@@ -145,6 +148,7 @@ __global__ __launch_bounds__(64) void sample_stage2_kernel(const float* __restri
   int i = part_i[b * kParts + threadIdx.x];
   wave_argmax(v, i);
   if (threadIdx.x == 0) {
+    if (i == 0x7fffffff) i = 0;  // nothing comparable in the row (all NaN): never emit an id outside [0, V)
     next[b] = i;
     advance(st, b, i);
   }
@@ -154,6 +158,7 @@ __global__ __launch_bounds__(64) void sample_stage2_kernel(const float* __restri
 // top-k / top-p (exact radix select), one 1024-thread block per row
 __device__ __forceinline__ uint32_t fkey(float f) {
   const uint32_t u = __float_as_uint(f);
+  if (u == 0x80000000u) return u;  // -0 gets the key of +0: equal floats, equal keys
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
@@ -252,7 +257,9 @@ __global__ __launch_bounds__(kTKThreads) void sample_topkp_kernel(const float* _
         float rem = sh_rem;
         int bin = 255;
         for (; bin > 0; --bin) {
-          if (mass[bin] >= rem) break;
+          // mass > 0: with top_p <= 0 (rem <= 0) stop at the first non-empty bin, i.e. the row maximum
+          // (mass exp(0) = 1), so the top-1 tie group survives; for rem > 0 the test is implied
+          if (mass[bin] >= rem && mass[bin] > 0.f) break;
           rem -= mass[bin];
         }
         sh_rem = rem;
@@ -280,6 +287,7 @@ __global__ __launch_bounds__(kTKThreads) void sample_topkp_kernel(const float* _
   __syncthreads();
   if (threadIdx.x == 0) {
     for (int w = 1; w < kTKThreads / 64; ++w) argmax_merge(bv, bi, sv[w], si[w]);
+    if (bi == 0x7fffffff) bi = 0;  // no survivor (all-NaN row): never emit an id outside [0, V)
     next[b] = bi;
     advance(st, b, bi);
   }

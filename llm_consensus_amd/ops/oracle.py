@@ -168,6 +168,7 @@ def philox_draw(key: int, idx: torch.Tensor, step: int) -> torch.Tensor:
 
 def gumbel(key: int, idx: torch.Tensor, step: int) -> torch.Tensor:
     r = philox_draw(key, idx, step)
+    # as on the device, 0xFFFFFF + 0.5 rounds up to 2^24 in float32: u = 1 and g = +inf for that draw
     u = ((r >> 8).float() + 0.5) * (1.0 / 16777216.0)
     return -torch.log(-torch.log(u))
 
@@ -202,7 +203,8 @@ def sample(logits: torch.Tensor, inv_temp, top_k, top_p, seeds, positions) -> to
             g = gumbel(int(seeds[b]), idx, int(positions[b]))
             v = torch.where(keep, row * it + g, torch.tensor(float("-inf")))
         mx = v.max()
-        out[b] = int(torch.nonzero(v == mx)[0].item())
+        hit = torch.nonzero(v == mx)
+        out[b] = int(hit[0].item()) if hit.numel() else 0  # all-NaN row: id 0, as the kernels write
     return out
 
 

@@ -6,6 +6,7 @@ import math
 import pytest
 import torch
 
+import sampler_ref
 from llm_consensus_amd import ops
 from llm_consensus_amd.ops import oracle
 
@@ -640,8 +641,8 @@ def test_sample_topk_topp_and_advance(cuda):
                block_tables=bt, bs=4, out_tokens=ot, out_count=oc, use_topkp=True)
     n = nxt.cpu()
     assert int(n[0]) == int(logits[0].argmax())
-    top50 = set(torch.topk(logits[1], 50).indices.cpu().tolist())
-    assert int(n[1]) in top50
+    # exact token of the float64 top-k/top-p reference when the row is decided (sampler_ref.py)
+    sampler_ref.check_row(int(n[1]), logits[1].cpu(), 1.0, 50, 0.9, 8, 6)
     assert pos.cpu().tolist() == [6, 7] and sl.cpu().tolist() == [7, 8]
     assert slots.cpu().tolist() == [int(bt[0, 1]) * 4 + 2, int(bt[1, 1]) * 4 + 3]
     assert oc.cpu().tolist() == [1, 1] and ot[:, 0].cpu().tolist() == n.tolist() and tin.cpu().tolist() == n.tolist()
