@@ -44,6 +44,8 @@ int llmc_gemm_kind(const void*, int, const void*, int, void*, int, int, int, int
 int llmc_gemm_plan(int, int);
 int llmc_rope_kv_write(const void*, int, void*, int, const void*, const void*, const void*, void*, void*, const void*,
                        int, int, int, int, int, const void*, hipStream_t);
+int llmc_qk_norm_rope_kv_write(const void*, int, void*, int, const void*, const void*, const void*, void*, void*,
+                               const void*, int, int, int, int, int, const void*, const void*, float, hipStream_t);
 int llmc_attn_decode_groups(int);
 int llmc_qkv_attn_check(int, int, int, int);
 int llmc_qkv_attn(const void*, const void*, float, const void*, int, void*, void*, void*, const void*, const void*,
@@ -212,6 +214,14 @@ PYBIND11_MODULE(_llmc_hip, m) {
      py::arg("cos_t"), py::arg("sin_t"), py::arg("k_cache"), py::arg("v_cache"), py::arg("slots"), py::arg("T"),
      py::arg("nh"), py::arg("nkv"), py::arg("D"), py::arg("bs"), py::arg("stream"),
      py::arg("bias") = 0);  // bias: bf16 [(nh + 2 nkv) D] in the qkv columns' order (16-B aligned), 0 = none
+  // Qwen3: rope_kv_write with a per-head RMSNorm (q_norm / k_norm bf16 [D], canonical order) before the rotation
+  m.def("qk_norm_rope_kv_write", [](ptr qkv, int qs, ptr qo, int qos, ptr pos, ptr cos_t, ptr sin_t, ptr kc, ptr vc,
+                                    ptr slots, int T, int nh, int nkv, int D, int bs, ptr q_norm, ptr k_norm,
+                                    float eps, ptr s) {
+    check(llmc_qk_norm_rope_kv_write(P(qkv), qs, P(qo), qos, P(pos), P(cos_t), P(sin_t), P(kc), P(vc), P(slots), T, nh,
+                                     nkv, D, bs, P(q_norm), P(k_norm), eps, S(s)),
+          "qk_norm_rope_kv_write");
+  });
   m.def("attn_decode_groups", [](int max_chunks) { return llmc_attn_decode_groups(max_chunks); });
   m.def("qkv_attn_check", [](int nh, int nkv, int D, int K) { return llmc_qkv_attn_check(nh, nkv, D, K); });
   m.def("qkv_attn", [](ptr x, ptr nw, float eps, ptr W, int K, ptr qo, ptr kc, ptr vc, ptr pos, ptr slots, ptr cos_t,

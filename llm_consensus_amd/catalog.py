@@ -85,6 +85,7 @@ def describe(name: str, tp: Optional[int] = None) -> Dict:
         "experts": c.n_experts, "top_k": c.top_k_experts,
         **({"sliding_window": c.sliding_window} if c.sliding_window else {}),
         **({"qkv_bias": True} if c.qkv_bias else {}),
+        **({"qk_norm": True} if c.qk_norm else {}),
         **({"path": c.checkpoint} if c.checkpoint else {}),
     }
 

@@ -371,6 +371,9 @@ class Engine:
         bf = dict(dtype=torch.bfloat16, device=dev)
         self.h = torch.zeros(B, c.hidden, **bf)
         self.q = torch.zeros(B, self.w.q_size, **bf)
+        # Qwen3 (per-head q/k norm): the decode projection's bf16 qkv rows, between its GEMV and the
+        # norm + RoPE launch (ops.qkv_rope's qkv_buf)
+        self.qkv_buf = torch.zeros(B, self.w.qkv_size, **bf) if c.qk_norm else None
         self.attn = torch.zeros(B, self.w.q_size, **bf)
         self.act = torch.zeros(B, self.w.inter, **bf)
         self.logits_local = torch.zeros(B, self.w.vocab_local, dtype=torch.float32, device=dev)
@@ -391,8 +394,12 @@ class Engine:
         # bucket keeps qkv_rope + attn_decode + o_proj. A window no sequence of this engine can
         # outgrow (W >= the longest context) masks nothing: such an engine runs unwindowed.
         self.window = int(c.sliding_window) if 0 < c.sliding_window < ctxmax else 0
+        # (attn_oproj's shape check takes H and K_o = nh D apart and the launch has run with K_o <= H:
+        # whole models and TP shards. A head_dim decoupled from hidden / heads can give K_o > H (Qwen3-4B:
+        # 4096 over 2560, a grid of 20 blocks per kv head); the check does not refuse that and the kernel
+        # has never run it, so such a model keeps the two launches)
         if (self.on_gpu and self.ecfg.attn_oproj and B == 1 and self.bs % 32 == 0 and not self.window
-                and (self.tp.size == 1 or self.ecfg.tp_attn_oproj)):
+                and c.q_size <= c.hidden and (self.tp.size == 1 or self.ecfg.tp_attn_oproj)):
             self.ao_nc = ops.attn_oproj_grid(c.hidden, self.nh, self.nkv, self.D)
             if self.ao_nc:
                 lo = self.ecfg.attn_oproj_min_chunk
@@ -406,9 +413,10 @@ class Engine:
         # their steps). Default: the fused-form buckets of short-qkv shards where attn_oproj does not
         # run; "all": every bucket, ahead of attn_oproj, the long ones as 256-key chunks
         self.qa_plan: List[Optional[tuple]] = [None] * len(self.attn_buckets)
-        # (qkv_attn has no place for a q/k/v bias either: Qwen2 models keep qkv_rope + attn_decode,
-        # or attn_oproj, which does not project qkv, where its own check passes)
-        if (self.on_gpu and B == 1 and not self.window and not c.qkv_bias
+        # (qkv_attn has no place for a q/k/v bias either, nor for Qwen3's per-head q/k norm: those
+        # models keep qkv_rope + attn_decode, or attn_oproj, which does not project qkv, where its own
+        # check passes)
+        if (self.on_gpu and B == 1 and not self.window and not c.qkv_bias and not c.qk_norm
                 and ops.qkv_attn_supported(self.nh, self.nkv, self.D, c.hidden)):
             self.qa_plan, self.ao_chunks = qkv_attn_plan(self.attn_buckets, self.ao_chunks, str(self.ecfg.qkv_attn),
                                                          (self.nh + 2 * self.nkv) * self.D, self.bs)
@@ -562,7 +570,8 @@ class Engine:
                 xn = ops.rmsnorm(h, Lw.ln1, c.rms_eps)
             qkv = ops.linear(xn, Lw.w_qkv, EPI_BF16)
             ops.rope_kv_write(qkv, pos_d, self.cos_t, self.sin_t, self.k_cache[li], self.v_cache[li], slots_d,
-                              self.nh, self.nkv, self.D, self.bs, qbuf, bias=Lw.b_qkv)
+                              self.nh, self.nkv, self.D, self.bs, qbuf, bias=Lw.b_qkv, q_norm=Lw.q_norm,
+                              k_norm=Lw.k_norm, qk_eps=c.rms_eps)
             ops.attn_prefill(qbuf, self.k_cache[li], self.v_cache[li], bt, qs_d, ql_d, cl_d, attn, max_qlen,
                              self.nh, self.nkv, self.D, self.bs, self.scale, max_ctx=max_ctx, ksplit=ksplit, kmin=kmin,
                              ws=pws, window=self.window)
@@ -777,7 +786,8 @@ class Engine:
             else:
                 ops.qkv_rope(h, Lw.w_qkv, Lw.ln1, c.rms_eps, q, self.k_cache[li], self.v_cache[li],
                              self.positions[:B], self.slots[:B], self.cos_t, self.sin_t, self.nh, self.nkv, self.D,
-                             self.bs, mfma=self.mfma_decode, Wp=Lw.p_qkv if pk else None, bias=Lw.b_qkv)
+                             self.bs, mfma=self.mfma_decode, Wp=Lw.p_qkv if pk else None, bias=Lw.b_qkv,
+                             q_norm=Lw.q_norm, k_norm=Lw.k_norm, qk_eps=c.rms_eps, qkv_buf=self.qkv_buf)
                 if ao_chunk:  # one-row engines: attention + o_proj + residual (+ TP all-reduce) in one launch
                     routed = self.ao_router[bi] and h.is_cuda  # ... (+ the MoE router)
                     self._attn_oproj(q, li, Lw, h, attn, ao_chunk, routed)

@@ -5,9 +5,10 @@ The reference has no local models at all: every "model" is a remote API (``inter
 Here a directory in Hugging Face layout becomes a first-class catalog family
 (``--weights-dir``), served by the same engine and kernels as the random-init architectures:
 
-* ``config_from_hf(dir)`` maps ``config.json`` (model_type llama / mistral / qwen2 / mixtral / phi3;
-  Mistral and Qwen2 checkpoints have the Llama layer layout, Qwen2 with a bias on q/k/v:
-  ``ModelConfig.qkv_bias``) to a :class:`ModelConfig` (Llama-3.1
+* ``config_from_hf(dir)`` maps ``config.json`` (model_type llama / mistral / qwen2 / qwen3 / mixtral / phi3;
+  Mistral, Qwen2 and Qwen3 checkpoints have the Llama layer layout, Qwen2 with a bias on q/k/v:
+  ``ModelConfig.qkv_bias``, Qwen3 with a per-head RMSNorm on q and k and an explicit ``head_dim``:
+  ``ModelConfig.qk_norm``) to a :class:`ModelConfig` (Llama-3.1
   ``rope_scaling`` included) that records the checkpoint path and the tokenizer's BOS / EOS ids. A
   ``sliding_window`` shorter than the context becomes ``ModelConfig.sliding_window`` (one window for
   every layer: Mistral-7B, Phi-3-mini-4k);
@@ -18,7 +19,7 @@ Here a directory in Hugging Face layout becomes a first-class catalog family
   (``block_sparse_moe.experts.{e}.w1/w2/w3``) and the fused one written by transformers 5
   (``mlp.experts.gate_up_proj``) are understood.
 
-Unsupported checkpoint features (o_proj / MLP biases, ``qwen2_moe``, per-layer sliding windows (``layer_types`` /
+Unsupported checkpoint features (o_proj / MLP biases, ``qwen2_moe``, ``qwen3_moe``, YaRN, per-layer sliding windows (``layer_types`` /
 ``max_window_layers`` that differ between layers), partial rotary, LongRoPE) raise :class:`CheckpointError` instead of running a wrong model.
 """
 
@@ -57,11 +58,13 @@ def config_from_hf(path: str, name: Optional[str] = None) -> ModelConfig:
     """ModelConfig of the Hugging Face checkpoint directory ``path``."""
     hc = _read_json(os.path.join(path, "config.json"))
     mt = hc.get("model_type", "")
-    arch = {"llama": "llama", "mistral": "llama", "qwen2": "llama", "mixtral": "mixtral", "phi3": "phi3"}.get(mt)
+    arch = {"llama": "llama", "mistral": "llama", "qwen2": "llama", "qwen3": "llama", "mixtral": "mixtral",
+            "phi3": "phi3"}.get(mt)
     if arch is None:
-        raise CheckpointError(f"{path}: model_type {mt!r} not supported (llama, mistral, qwen2, mixtral, phi3)")
+        raise CheckpointError(f"{path}: model_type {mt!r} not supported (llama, mistral, qwen2, qwen3, mixtral, phi3)")
     # qwen2: a bias on q/k/v and nowhere else, by architecture (its config has no flag for it).
-    # attention_bias on a llama / mistral config puts one on o_proj too, mlp_bias on the MLP
+    # attention_bias on a llama / mistral / qwen3 config puts one on o_proj too, mlp_bias on the MLP.
+    # qwen3: no bias, a per-head RMSNorm on q and k instead (no flag for it either)
     if hc.get("attention_bias") or hc.get("mlp_bias"):
         raise CheckpointError(f"{path}: o_proj / MLP biases (attention_bias, mlp_bias) are not supported; "
                               "only the q/k/v biases of model_type qwen2 are")
@@ -130,6 +133,7 @@ def config_from_hf(path: str, name: Optional[str] = None) -> ModelConfig:
         tie_embeddings=bool(hc.get("tie_word_embeddings", False)),
         sliding_window=window,
         qkv_bias=mt == "qwen2",
+        qk_norm=mt == "qwen3",
     )
 
 
@@ -213,6 +217,8 @@ class HFCheckpoint:
             return torch.cat([self.raw(p + f"self_attn.{x}_proj.weight") for x in "qkv"], 0)
         if leaf == "b_qkv":  # Qwen2: q | k | v biases, in the row order of w_qkv
             return torch.cat([self.raw(p + f"self_attn.{x}_proj.bias") for x in "qkv"], 0)
+        if leaf in ("q_norm", "k_norm"):  # Qwen3: [head_dim], shared by the layer's heads
+            return self.raw(p + f"self_attn.{leaf}.weight")
         if leaf == "w_o":
             return self.raw(p + "self_attn.o_proj.weight")
         if leaf == "w_gu":

@@ -24,7 +24,7 @@ class RopeScaling:
 @dataclasses.dataclass(frozen=True)
 class ModelConfig:
     name: str
-    arch: str  # "llama" (also Mistral, Qwen2: the same layer layout) | "mixtral" | "phi3"
+    arch: str  # "llama" (also Mistral, Qwen2, Qwen3: the same layer layout) | "mixtral" | "phi3"
     n_layers: int
     hidden: int
     n_heads: int
@@ -50,6 +50,10 @@ class ModelConfig:
     # a bias on the q, k and v projections (Qwen2 / Qwen2.5; o_proj and the MLP have none), added
     # before the rotation
     qkv_bias: bool = False
+    # an RMSNorm over the head dimension on every q and every k head, after the projection and
+    # before the rotation (Qwen3; weights [head_dim], one vector for the layer's q heads, one for
+    # its k heads)
+    qk_norm: bool = False
 
     @property
     def eos(self) -> tuple:
@@ -77,7 +81,7 @@ class ModelConfig:
         attn = h * self.qkv_size + self.q_size * h + (self.qkv_size if self.qkv_bias else 0)
         mlp = 3 * h * i * (self.n_experts if self.is_moe else 1)
         router = h * self.n_experts if self.is_moe else 0
-        per_layer = attn + mlp + router + 2 * h
+        per_layer = attn + mlp + router + 2 * h + (2 * self.head_dim if self.qk_norm else 0)
         return self.n_layers * per_layer + 2 * self.vocab * h + h
 
     def weight_bytes(self, dtype_bytes: int = 2) -> int:
@@ -152,6 +156,13 @@ QWEN25_7B = ModelConfig("qwen2.5-7b", "llama", 28, 3584, 28, 4, 128, 18944, 1520
 # multiple of 128, heads / FFN / vocab shardable over TP = 2
 QWEN2_TINY = ModelConfig("qwen2-tiny", "llama", 2, 896, 14, 2, 64, 1024, 1024, 1000000.0, rms_eps=1e-6,
                          max_position=4096, qkv_bias=True)
+# Qwen3 (dense): no q/k/v bias, an explicit head_dim, a per-head RMSNorm on q and k before the rotation
+QWEN3_8B = ModelConfig("qwen3-8b", "llama", 36, 4096, 32, 8, 128, 12288, 151936, 1000000.0, rms_eps=1e-6,
+                       max_position=40960, qk_norm=True)
+# Qwen3's shape class in small: heads of 128 over a hidden of 256 (q_size 512: the head_dim decoupled
+# from hidden / heads, as in Qwen3-0.6B / 1.7B / 4B), heads / FFN / vocab shardable over TP = 2
+QWEN3_TINY = ModelConfig("qwen3-tiny", "llama", 2, 256, 4, 2, 128, 512, 1024, 1000000.0, rms_eps=1e-6,
+                         max_position=4096, qk_norm=True)
 # llama-tiny with a window short enough that tiny prompts cross it
 MISTRAL_TINY = LLAMA_TINY.with_(name="mistral-tiny", sliding_window=48)
 # tiny stand-in for Llama-3-70B in TP=4 rehearsals (heads, kv heads, FFN and vocab shard over 4)
@@ -160,7 +171,7 @@ LLAMA_TINY_TP4 = ModelConfig("llama-tiny-tp4", "llama", 2, 512, 8, 4, 64, 1024, 
 
 FAMILIES = {c.name: c for c in (LLAMA3_8B, LLAMA3_70B, MIXTRAL_8X7B, PHI3_MINI,
                                 LLAMA_TINY, LLAMA_SMALL, MIXTRAL_TINY, PHI3_TINY, LLAMA_TINY_TP4,
-                                MISTRAL_7B, MISTRAL_TINY, QWEN25_7B, QWEN2_TINY)}
+                                MISTRAL_7B, MISTRAL_TINY, QWEN25_7B, QWEN2_TINY, QWEN3_8B, QWEN3_TINY)}
 
 
 def rope_inv_freq(cfg: ModelConfig):

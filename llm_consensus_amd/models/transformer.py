@@ -6,7 +6,9 @@ checkpoint compatibility:
     K head the rows are PAIR-INTERLEAVED (row 2i = dim i, row 2i + 1 = dim i + D/2) so the
     rotate-half RoPE pair of a head lands in one wave of the decode GEMV, whose epilogue applies
     RoPE and writes K/V straight into the paged cache (no separate RoPE launch); ``b_qkv``
-    [q + 2 kv] (Qwen2 only) is the projection's bias in the same row order;
+    [q + 2 kv] (Qwen2 only) is the projection's bias in the same row order; ``q_norm`` / ``k_norm``
+    [D] (Qwen3 only) are the per-head q/k RMSNorm weights in canonical order, applied between the
+    projection and the rotation by a launch of their own (csrc/kernels/qk_norm_rope.hip);
   * ``w_o``    [H, q];
   * ``w_gu``   [2 I, H] gate/up rows INTERLEAVED (row 2i = gate_i, 2i + 1 = up_i) so the GEMV
     epilogue produces silu(gate) * up directly and a TP shard is a contiguous row range;
@@ -35,7 +37,10 @@ from .config import ModelConfig
 class LayerWeights:
     # b_qkv: the q/k/v projection bias [qkv_size_local] (cfg.qkv_bias; None otherwise), sharded and
     # pair-interleaved exactly as the rows of w_qkv: b_qkv[n] belongs to w_qkv[n]
-    TENSORS = ("ln1", "ln2", "w_qkv", "w_o", "w_gu", "w_down", "w_router", "b_qkv")
+    # q_norm / k_norm: the per-head q/k RMSNorm weights [head_dim] (cfg.qk_norm, Qwen3; None otherwise) in
+    # CANONICAL dimension order (the kernel pairs g[i] with g[i + D/2] itself), replicated on every TP
+    # rank: the norm is per head and heads are sharded whole
+    TENSORS = ("ln1", "ln2", "w_qkv", "w_o", "w_gu", "w_down", "w_router", "b_qkv", "q_norm", "k_norm")
     # p_*: the packed twin (ops.wpack: PackedWeight / PackedWeight12; PackedExperts12 of a MoE layer's w_gu and
     # w_down stacks) of w_*, or None: decode streams bf16
     PACKED = ("p_qkv", "p_o", "p_gu", "p_down")
@@ -142,6 +147,13 @@ class TransformerWeights:
                     bv = b[c.q_size + c.kv_size + k0 * D:c.q_size + c.kv_size + k1 * D]
                     L.b_qkv = torch.cat([pair_interleave_heads(bq, D), pair_interleave_heads(bk, D), bv],
                                         0).reshape(-1).contiguous()
+                if c.qk_norm:
+                    # std 0.3 around 1, not the 0.02 of the other norms: with g ~ 1 a dropped, swapped or
+                    # wrongly ordered g would go unnoticed
+                    for nm in ("q_norm", "k_norm"):
+                        g = (self._full(p + nm, (D,)) if self.source is not None
+                             else self._gen(p + nm, (D,), 0.3, 1.0))
+                        setattr(L, nm, g.contiguous())
                 wo = self._linear(p + "w_o", c.hidden, c.q_size)
                 L.w_o = wo[:, q0 * D:q1 * D].contiguous()
                 del wo

@@ -228,30 +228,87 @@ def _qkv_bias(bias, n: int, name: str):
     return bias
 
 
-def rope_kv_write(qkv, positions, cos_t, sin_t, k_cache, v_cache, slots, nh, nkv, D, bs, q_out, bias=None) -> None:
+QK_NORM_HEAD_DIMS = (64, 128)  # head dims of the per-head q/k norm kernel (qk_norm_rope.hip)
+
+
+def _qk_norms(q_norm, k_norm, bias, D: int, name: str) -> bool:
+    """Checks the per-head q/k norm weights of a launch (Qwen3; bf16 [D] each, or both None);
+    True when the launch has them."""
+    if q_norm is None and k_norm is None:
+        return False
+    if q_norm is None or k_norm is None:
+        raise ValueError(f"{name}: q_norm and k_norm come together")
+    if bias is not None:
+        raise ValueError(f"{name}: a q/k norm together with a q/k/v bias is not a supported model")
+    for g, what in ((q_norm, "q_norm"), (k_norm, "k_norm")):
+        _bf16(g, f"{name}.{what}")
+        if g.dim() != 1 or g.numel() != D or not g.is_contiguous():
+            raise ValueError(f"{name}: {what} must be a contiguous tensor of {D} elements, got {tuple(g.shape)}")
+    return True
+
+
+def rope_kv_write(qkv, positions, cos_t, sin_t, k_cache, v_cache, slots, nh, nkv, D, bs, q_out, bias=None,
+                  q_norm=None, k_norm=None, qk_eps: float = 1e-6) -> None:
     """Prefill RoPE: pair-interleaved Q/K rows of ``qkv`` -> canonical rotated q in ``q_out``,
     rotated k and raw v into the paged cache. ``bias`` (Qwen2; bf16 [(nh + 2 nkv) D] in the order
     of the qkv columns): added in f32 to the bf16 row, Q/K before the rotation, V as
-    bf16(f32(v) + f32(b))."""
+    bf16(f32(v) + f32(b)). ``q_norm`` / ``k_norm`` (Qwen3; bf16 [D], canonical dimension order, one
+    vector for all Q heads and one for all K heads): every Q / K head is RMS-normalised over its D
+    dims (``qk_eps``) in f32 before the rotation, in the launch of csrc/kernels/qk_norm_rope.hip
+    (D = 64 or 128; another D raises). Norms together with a ``bias`` raise ``ValueError``."""
+    normed = _qk_norms(q_norm, k_norm, bias, D, "rope_kv_write")
     if not qkv.is_cuda:
-        oracle.rope_kv_write(qkv, positions, cos_t, sin_t, k_cache, v_cache, slots, nh, nkv, D, bs, q_out, bias)
+        oracle.rope_kv_write(qkv, positions, cos_t, sin_t, k_cache, v_cache, slots, nh, nkv, D, bs, q_out, bias,
+                             q_norm, k_norm, qk_eps)
         return
     T = qkv.shape[0]
+    if normed:
+        _bf16(qkv, "rope_kv_write.qkv")
+        if D not in QK_NORM_HEAD_DIMS:
+            raise ValueError(f"rope_kv_write: the q/k norm kernel covers head dims {QK_NORM_HEAD_DIMS}, got {D}")
+        if not (q_norm.is_cuda and k_norm.is_cuda):
+            raise ValueError("rope_kv_write: q_norm / k_norm must be on the GPU")
+        if (qkv.shape[1] < (nh + 2 * nkv) * D or q_out.shape[0] < T or q_out.shape[1] < nh * D
+                or positions.numel() < T or (slots is not None and slots.numel() < T)):
+            raise ValueError(f"rope_kv_write: qkv {tuple(qkv.shape)} / q_out {tuple(q_out.shape)} / positions / "
+                             f"slots do not cover {T} rows of ({nh} + 2 x {nkv}) heads of {D}")
+        kernels().qk_norm_rope_kv_write(_p(qkv), qkv.stride(0), _p(q_out), q_out.stride(0), _p(positions), _p(cos_t),
+                                        _p(sin_t), _p(k_cache), _p(v_cache), _p(slots), T, nh, nkv, D, bs,
+                                        _p(q_norm), _p(k_norm), float(qk_eps), _s(qkv))
+        return
     bias = _qkv_bias(bias, (nh + 2 * nkv) * D, "rope_kv_write")
     kernels().rope_kv_write(_p(qkv), qkv.stride(0), _p(q_out), q_out.stride(0), _p(positions), _p(cos_t), _p(sin_t),
                             _p(k_cache), _p(v_cache), _p(slots), T, nh, nkv, D, bs, _s(qkv), _p(bias))
 
 
 def qkv_rope(x, W, norm_w, eps, q_out, k_cache, v_cache, positions, slots, cos_t, sin_t, nh, nkv, D, bs,
-             mfma: bool = False, Wp: Optional["wpack.PackedWeight"] = None, bias=None) -> None:
+             mfma: bool = False, Wp: Optional["wpack.PackedWeight"] = None, bias=None,
+             q_norm=None, k_norm=None, qk_eps: float = 1e-6, qkv_buf: Optional[torch.Tensor] = None) -> None:
     """Decode qkv projection: fused RMSNorm prologue + RoPE/KV-write epilogue (one launch; form and
     ``Wp`` as ``linear``). ``bias`` (Qwen2; bf16 [N], ``bias[n]`` belongs to ``W[n]``): added to the
-    f32 accumulators before the rotation, and on the V rows."""
+    f32 accumulators before the rotation, and on the V rows.
+
+    ``q_norm`` / ``k_norm`` (Qwen3; as ``rope_kv_write``): the per-head norm needs a whole head's sum
+    of squares, which the GEMV's epilogue (1-2 rows per wave) cannot form, so the projection becomes
+    two launches: ``linear(..., EPI_BF16, out=qkv_buf)`` (the packed twin or the MFMA form exactly as
+    ``linear`` chooses) and ``rope_kv_write`` with the norms on ``qkv_buf``, a caller-owned bf16
+    [>= M, N] buffer (required on the GPU: nothing is allocated inside a captured graph)."""
+    normed = _qk_norms(q_norm, k_norm, bias, D, "qkv_rope")
     if not x.is_cuda:
         qkv = oracle.linear(x, W, EPI_BF16, None, norm_w, eps)
-        oracle.rope_kv_write(qkv, positions, cos_t, sin_t, k_cache, v_cache, slots, nh, nkv, D, bs, q_out, bias)
+        oracle.rope_kv_write(qkv, positions, cos_t, sin_t, k_cache, v_cache, slots, nh, nkv, D, bs, q_out, bias,
+                             q_norm, k_norm, qk_eps)
         return
     M, K = x.shape
+    if normed:
+        N = W.shape[0]
+        if (qkv_buf is None or qkv_buf.dtype != torch.bfloat16 or qkv_buf.dim() != 2 or qkv_buf.shape[0] < M
+                or qkv_buf.shape[1] != N or N != (nh + 2 * nkv) * D):
+            raise ValueError(f"qkv_rope: the q/k norm needs qkv_buf, bf16 [>= {M}, {N}]")
+        qkv = linear(x, W, EPI_BF16, out=qkv_buf[:M], norm_w=norm_w, eps=eps, mfma=mfma, Wp=Wp)
+        rope_kv_write(qkv, positions, cos_t, sin_t, k_cache, v_cache, slots, nh, nkv, D, bs, q_out,
+                      q_norm=q_norm, k_norm=k_norm, qk_eps=qk_eps)
+        return
     bias = _qkv_bias(bias, W.shape[0], "qkv_rope")
     if _use_packed(Wp, M, W.shape[0], K, mfma):
         qkv_packed = (kernels().gemv_qkv_rope_p12 if isinstance(Wp, wpack.PackedWeight12)

@@ -62,11 +62,31 @@ def rope_tables(inv_freq, max_pos: int):
     return torch.cos(ang).float(), torch.sin(ang).float()
 
 
-def rope_kv_write(qkv, positions, cos_t, sin_t, k_cache, v_cache, slots, nh, nkv, D, bs, q_out, bias=None):
+def qk_head_norm(x1, x2, nh, q_norm, k_norm, eps):
+    """Qwen3's per-head RMSNorm on the rotation halves of the Q and K heads: ``x1`` / ``x2`` f32
+    [..., nh + nkv, D/2] hold dims [0, D/2) / [D/2, D) of every head (Q heads first); ``q_norm`` /
+    ``k_norm`` [D] in canonical order, one vector for all Q heads, one for all K heads. ``rmsnorm``'s
+    convention in f32, with no bf16 rounding of the result (the rotation follows in f32)."""
+    x = torch.cat([x1, x2], dim=-1)  # canonical [..., heads, D]
+    inv = torch.rsqrt(x.pow(2).mean(-1, keepdim=True) + eps)
+    g = torch.cat([q_norm.float().expand(nh, -1), k_norm.float().expand(x.shape[-2] - nh, -1)]).to(x.device)
+    y = x * inv * g
+    half = x1.shape[-1]
+    return y[..., :half], y[..., half:]
+
+
+def rope_kv_write(qkv, positions, cos_t, sin_t, k_cache, v_cache, slots, nh, nkv, D, bs, q_out, bias=None,
+                  q_norm=None, k_norm=None, qk_eps: float = 1e-6):
     """qkv rows hold Q and K heads PAIR-INTERLEAVED ([x0, x_h, x1, x_{h+1}, ...], h = D/2);
     rotated Q goes to ``q_out`` [T, nh*D] in canonical order, rotated K / raw V to the cache.
     ``bias`` [(nh + 2 nkv) D] (Qwen2; in the order of the qkv columns) is added in f32 to the row
-    it is given: Q/K before the rotation, V as bf16(f32(v) + f32(b))."""
+    it is given: Q/K before the rotation, V as bf16(f32(v) + f32(b)). ``q_norm`` / ``k_norm`` [D]
+    (Qwen3; canonical order): every Q / K head is RMS-normalised over its D dims in f32 before the
+    rotation (``qk_head_norm``): x * rsqrt(mean(x^2) + qk_eps) * g, rounded to bf16 only after it."""
+    if (q_norm is None) != (k_norm is None):
+        raise ValueError("rope_kv_write: q_norm and k_norm come together")
+    if q_norm is not None and bias is not None:
+        raise ValueError("rope_kv_write: a q/k norm together with a q/k/v bias is not a supported model")
     T = qkv.shape[0]
     half = D // 2
     pos = positions.long()
@@ -77,6 +97,8 @@ def rope_kv_write(qkv, positions, cos_t, sin_t, k_cache, v_cache, slots, nh, nkv
         qkf = qkf + bias[: (nh + nkv) * D].float()
     qk = qkf.view(T, nh + nkv, half, 2)
     x1, x2 = qk[..., 0], qk[..., 1]
+    if q_norm is not None:
+        x1, x2 = qk_head_norm(x1, x2, nh, q_norm, k_norm, qk_eps)
     rot = torch.cat([x1 * c - x2 * s, x2 * c + x1 * s], dim=-1).to(torch.bfloat16)
     q_out[:, : nh * D] = rot[:, :nh].reshape(T, nh * D)
     if slots is not None:
@@ -310,6 +332,8 @@ def reference_logits(w, cfg, ids, out_pos, cos_t: torch.Tensor, sin_t: torch.Ten
                              (qkv[:, (nh + nkv) * D:].float() + L.b_qkv[(nh + nkv) * D:].float()).to(bf).float()], 1)
         qk = qkv[:, : (nh + nkv) * D].view(T, nh + nkv, half, 2).float()
         x1, x2 = qk[..., 0], qk[..., 1]
+        if getattr(L, "q_norm", None) is not None:  # Qwen3: per-head RMSNorm, as rope_kv_write
+            x1, x2 = qk_head_norm(x1, x2, nh, L.q_norm, L.k_norm, cfg.rms_eps)
         rot = torch.cat([x1 * cos - x2 * sin, x2 * cos + x1 * sin], dim=-1).to(bf)  # [T, nh + nkv, D]
         q, k = rot[:, :nh].float(), rot[:, nh:].float()
         v = qkv[:, (nh + nkv) * D:(nh + 2 * nkv) * D].view(T, nkv, D).float()
@@ -381,6 +405,8 @@ def reference_decode_layer(L, cfg, h_in: torch.Tensor, k_cache: torch.Tensor, v_
     qk = qkv[: (nh + nkv) * D].view(nh + nkv, half, 2).float()
     c, sn = cos_t.to(dev)[pos].float(), sin_t.to(dev)[pos].float()
     x1, x2 = qk[..., 0], qk[..., 1]
+    if getattr(L, "q_norm", None) is not None:  # Qwen3: as reference_logits
+        x1, x2 = qk_head_norm(x1, x2, nh, L.q_norm, L.k_norm, cfg.rms_eps)
     rot = torch.cat([x1 * c - x2 * sn, x2 * c + x1 * sn], dim=-1).to(bf)  # [nh + nkv, D]
     q = rot[:nh].float().view(nkv, G, D)
     k_new = rot[nh:].float()

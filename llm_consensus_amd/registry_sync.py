@@ -41,6 +41,8 @@ def _record(source: str, rid: str, cfg, raw: bool) -> dict:
         rec["sliding_window"] = cfg.sliding_window
     if cfg.qkv_bias:
         rec["qkv_bias"] = True
+    if cfg.qk_norm:
+        rec["qk_norm"] = True
     if raw:
         d = dataclasses.asdict(cfg)
         d["eos_ids"] = list(d.get("eos_ids") or ())
@@ -48,6 +50,8 @@ def _record(source: str, rid: str, cfg, raw: bool) -> dict:
             d.pop("sliding_window", None)
         if not d.get("qkv_bias"):
             d.pop("qkv_bias", None)
+        if not d.get("qk_norm"):
+            d.pop("qk_norm", None)
         rec["raw"] = d
     return rec
 
