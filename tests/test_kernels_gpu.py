@@ -6,6 +6,7 @@ import math
 import pytest
 import torch
 
+import attn_probe
 import sampler_ref
 from llm_consensus_amd import ops
 from llm_consensus_amd.ops import oracle
@@ -422,6 +423,8 @@ def test_attn_decode_fused_long_context(cuda, nh, nkv, chunk, cap):
         ops.attn_decode(q, kc, vc, bt.cuda(), sl.cuda(), out, part, ctr, nh, nkv, D, bs, chunk, scale,
                         grid_chunks=gc, fused=True)
         close(out, ref, 2e-2)
+        attn_probe.assert_rms(out, attn_probe.dense_decode(q, kc, vc, bt, lens, nh, nkv, D, bs, scale),
+                              "decode_fused_long_context")
     tickets = torch.cat([ctr[..., :1, 0], ctr[..., 2:, 0]], dim=-1)
     assert int(tickets.abs().sum()) == 0, ctr
 
@@ -447,6 +450,7 @@ def test_attn_decode_wide_split(cuda, nh, nkv, gc):
         out.zero_()
         ops.attn_decode(q, kc, vc, bt.cuda(), sl.cuda(), out, part, ctr, nh, nkv, D, bs, 128, scale, grid_chunks=gc)
         close(out, ref, 2e-2)
+        attn_probe.assert_rms(out, attn_probe.dense_decode(q, kc, vc, bt, lens, nh, nkv, D, bs, scale), "decode_wide_split")
     tickets = torch.cat([ctr[..., :1, 0], ctr[..., 2:, 0]], dim=-1)
     assert int(tickets.abs().sum()) == 0, ctr
 
@@ -563,6 +567,8 @@ def test_attn_prefill_long_context_vs_fp32(cuda, nh, nkv, D, ctx, ksplit):
     oracle.attn_prefill(q, kc, vc, bt.cuda(), qs, ql, cl, nh, nkv, D, bs, scale, ref)  # fp32 math, on the GPU
     torch.cuda.synchronize()
     close(out, ref.float().cpu(), 2e-2)
+    attn_probe.assert_rms(out, attn_probe.dense_prefill(q, kc, vc, bt, qs.tolist(), qlens, ctxs, nh, nkv, D, bs, scale),
+                          "prefill_long_context")
 
 
 @pytest.mark.parametrize("nh,nkv,D,qlens", [(32, 8, 128, [2048]), (32, 8, 128, [1000, 700]), (32, 32, 96, [1024]),

@@ -8,6 +8,7 @@ import math
 import pytest
 import torch
 
+import attn_probe
 from llm_consensus_amd import ops
 from llm_consensus_amd.engine import Engine, EngineConfig
 from llm_consensus_amd.models.config import FAMILIES
@@ -106,6 +107,8 @@ def test_attn_decode_fused_window_long_context(cuda, nh, nkv, chunk, cap):
         ops.attn_decode(q, kc, vc, bt.cuda(), sl.cuda(), out, part, ctr, nh, nkv, D, bs, chunk, scale,
                         grid_chunks=gc, fused=True, window=W)
         close(out, ref, 2e-2)
+        attn_probe.assert_rms(out, attn_probe.dense_decode(q, kc, vc, bt, lens, nh, nkv, D, bs, scale, W),
+                              "decode_fused_window_long_context")
     tickets = torch.cat([ctr[..., :1, 0], ctr[..., 2:, 0]], dim=-1)
     assert int(tickets.abs().sum()) == 0, ctr
 
@@ -151,6 +154,8 @@ def test_attn_decode_split_window_two_level(cuda):
     ops.attn_decode(q, kc, vc, bt.cuda(), sl.cuda(), out, part, ctr, nh, nkv, D, bs, 128, scale, grid_chunks=gc,
                     window=39000)
     close(out, ref, 2e-2)
+    attn_probe.assert_rms(out, attn_probe.dense_decode(q, kc, vc, bt, lens, nh, nkv, D, bs, scale, 39000),
+                          "decode_split_window_two_level")
     tickets = torch.cat([ctr[..., :1, 0], ctr[..., 2:, 0]], dim=-1)
     assert int(tickets.abs().sum()) == 0, ctr
 
