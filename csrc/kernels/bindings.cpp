@@ -42,6 +42,7 @@ int llmc_gemm_t128(const void*, int, const void*, int, void*, int, int, int, int
 int llmc_gemm_narrow(const void*, int, const void*, int, void*, int, int, int, int, int, hipStream_t);
 int llmc_gemm_kind(const void*, int, const void*, int, void*, int, int, int, int, int, int, hipStream_t);
 int llmc_gemm_plan(int, int);
+int llmc_gemv_plan(int, int, int, int, int, int, int*);
 int llmc_rope_kv_write(const void*, int, void*, int, const void*, const void*, const void*, void*, void*, const void*,
                        int, int, int, int, int, const void*, hipStream_t);
 int llmc_qk_norm_rope_kv_write(const void*, int, void*, int, const void*, const void*, const void*, void*, void*,
@@ -202,6 +203,11 @@ PYBIND11_MODULE(_llmc_hip, m) {
     check(llmc_gemm_kind(P(A), lda, P(W), ldw, P(C), ldc, M, N, K, epi, kind, S(s)), "gemm_kind");
   });
   m.def("gemm_plan", [](int M, int N) { return llmc_gemm_plan(M, N); });
+  m.def("gemv_plan", [](int op, int M, int N, int K, int epi, int wf) {
+    int o[4];
+    check(llmc_gemv_plan(op, M, N, K, epi, wf, o), "gemv_plan");
+    return std::make_tuple(o[0], o[1], o[2], o[3] != 0);
+  });
   m.def("gemm_narrow", [](ptr A, int lda, ptr W, int ldw, ptr C, int ldc, int M, int N, int K, int epi, ptr s) {
     check(llmc_gemm_narrow(P(A), lda, P(W), ldw, P(C), ldc, M, N, K, epi, S(s)), "gemm_narrow");
   });

@@ -7,7 +7,7 @@
 //    c = l + 64 i (16 B = 8 bf16 each) of all RPW rows -> RPW*UNROLL independent 16 B loads in
 //    flight per lane, straight to VGPRs (no LDS round trip for W), non-temporal (read once).
 //  * Geometry (NT threads, RPW rows/wave) is chosen per shape on the host so the grid is a
-//    balanced multiple of the 256 CUs with >= 16 waves/CU in flight (launch_gemv in gemv.hip).
+//    balanced multiple of the 256 CUs with >= 16 waves/CU in flight (gemv_geom in gemv_geom.h).
 //  * x is staged ONCE per block in LDS (M*K bf16); every lane reads the same chunk index it
 //    loads from W, so ds_read_b128 addresses are lane-consecutive (conflict-free).
 //  * v_dot2_f32_bf16 does convert+multiply+accumulate of 2 elements per VALU op.
@@ -22,12 +22,11 @@
 
 #include "car_proto.h"
 #include "common.h"
+#include "gemv_geom.h"
 
 namespace llmc {
 
-enum { PRO_NONE = 0, PRO_NORM = 1 };
-enum { EPI_BF16 = 0, EPI_F32 = 1, EPI_RESADD = 2, EPI_SILU = 3, EPI_ROPE = 4, EPI_COMBINE = 5, EPI_AR = 6 };
-
+// PRO_*, EPI_*: gemv_geom.h.
 // EPI_AR: a tensor-parallel rank's row-parallel projection (decode o_proj / down_proj) with the
 // all-reduce in its own epilogue: h = sum over ranks of (W_r . x_r), rank 0's term carrying the
 // residual h. Block b of every rank owns the same rows, so block b only exchanges with block b
@@ -84,16 +83,15 @@ struct RopeEpi {
 // unit slot after the last whole one: its two or three loads fill the slot's registers where p12_chunk
 // expects chunks 0..tailq-1, it is issued one batch ahead like every unit, and its chunks are patched (q =
 // 4 units + c) and summed after the last whole unit's, which is the bf16 loop's order for the lane.
-enum { WF_BF16 = 0, WF_P13 = 1, WF_P12 = 2 };
-constexpr int kP13UnitElems = 2048, kP13UnitBytes = 3328, kP13Raw = 0xff;
+// (WF_*, kP13UnitElems, kP12ChunkElems, kP12MaxK: gemv_geom.h, the host rule needs them.)
+constexpr int kP13UnitBytes = 3328, kP13Raw = 0xff;
 constexpr int kP12UnitBytes = 3072, kP12Raw = 0xff, kP12MaxExc = 16, kP12RecDwords = 1 + kP12MaxExc;
-constexpr int kP12ChunkElems = 512, kP12TailChunkBytes = 768;  // a tail chunk: 512 low bytes, 256 nibble bytes
-constexpr int kP12MaxK = 65536 - kP13UnitElems;  // positions are 16 bits, and q = 127 marks the list's end
+constexpr int kP12TailChunkBytes = 768;  // a tail chunk: 512 low bytes, 256 nibble bytes
 constexpr uint32_t kP12End = 0xffffffffu;
 struct PackedW {
   const uint8_t* planes;  // P13 [N][K / 2048][3328] | P12 [N][K / 2048][3072] (+ [(K / 512) % 4][768] per row: the tail)
   const uint8_t* hdr;     // P13 [N] bytes (readable up to the next multiple of 4) | P12 [N][17] dwords
-  int wf = WF_P13;        // host side: which kernel reads it
+  int wf = WF_BF16;       // host side: which kernel reads it (WF_BF16: no twin, null planes)
 };
 struct P13Unit {  // one lane's share of a wave unit: 13 dwords for 32 weights
   u32x4 l0, l1, n;
@@ -116,25 +114,6 @@ __device__ __forceinline__ u32x4 p13_chunk(const P13Unit& p, uint32_t base4) {
   return w;
 }
 
-// The WF_P12 launch of the geometry (NT, RPW, UNROLL) that gemv.hip's launchers chose (gemv_p12.hip: the
-// P12 kernels are a translation unit of their own, compiled beside gemv.hip's); -8: not instantiated.
-int launch_gemv_p12(int M, int NT, int RPW, int UNROLL, int pro, int epi, const void* x, int x_stride, const void* nw,
-                    float eps, const void* W, const PackedW& pw, void* out, int out_stride, int N, int K,
-                    const RopeEpi& rope, hipStream_t s);
-// The WF_P12 launches of the MoE decode GEMVs (gemv_moe_p12.hip), pw the twin of the [E * N, K] view of the
-// expert stack W: the pair form in the geometry (NT, RPW) that gemv.hip's moe_gemv_geom chose, and the
-// down projection fused with the top-2 combine in llmc_moe_down_combine's fixed geometry. -8: not
-// instantiated (the caller launches the bf16 kernel: the same bits).
-int launch_moe_gemv_p12(int NT, int RPW, int pro, int epi, int npairs, const void* x, int x_stride, const void* nw,
-                        float eps, const void* W, const PackedW& pw, const void* ids, int x_div, void* out,
-                        int out_stride, int N, int K, hipStream_t s);
-int launch_moe_combine_p12(int T, const void* act, int act_stride, const void* W, const PackedW& pw, const void* ids,
-                           const void* w, void* h, int h_stride, int N, int K, hipStream_t s);
-// The WF_P12 launch of the row-parallel GEMV with the fused all-reduce (EPI_AR; gemv_ar_p12.hip) in the
-// geometry (NT, UNROLL) that gemv.hip's gemv_ar_geom chose. -8: not instantiated (the caller launches the
-// bf16 kernel: the same bits).
-int launch_gemv_ar_p12(int M, int NT, int UNROLL, const void* x, int x_stride, const void* W, const PackedW& pw, void* h,
-                       int h_stride, int N, int K, const CarArgs& ar, hipStream_t s);
 struct P12Unit {  // 12 dwords for 32 weights
   u32x4 l0, l1, n;
 };
@@ -169,7 +148,7 @@ __device__ __forceinline__ void p12_patch(u32x4& w, uint32_t ent, int lane) {
 // Batched decode (3 <= M <= 32 rows): the MFMA form in gemv_mfma.hip, same prologue/epilogues
 // (one 16-token MFMA column group up to 16 rows, two above). This kernel serves M <= kGemvMaxM
 // (and M <= 4 when K is not a multiple of 128). MoE pairs stay within one token group.
-constexpr int kGemvMaxM = 2, kGemvmMaxM = 32, kMoeGemvmMaxTokens = 16;
+constexpr int kGemvmMaxM = 32, kMoeGemvmMaxTokens = 16;  // kGemvMaxM: gemv_geom.h
 int gemvm_dispatch(int M, const void* x, int x_stride, const void* norm_w, float eps, const void* W, void* out,
                    int out_stride, int N, int K, int epi, const RopeEpi& rope, hipStream_t st, int form = 0);
 
@@ -895,6 +874,33 @@ __global__ __launch_bounds__(NT) void gemv_p12_kernel(const bf16_t* __restrict__
   extern __shared__ __attribute__((aligned(16))) char smem[];
   gemv_block<M, NT, RPW, UNROLL, PRO, EPI, false, WF_P12, DEPTH, TAIL>(blockIdx.x, blockIdx.y, smem, x, x_stride, norm_w, eps, W,
                                                           out, out_stride, N, K, nullptr, 1, rope, CarArgs{}, pw);
+}
+
+// WF_P12 form of the row-parallel GEMV with the all-reduce in its epilogue (EPI_AR)
+template <int M, int NT, int UNROLL, bool TAIL>
+__global__ __launch_bounds__(NT) void gemv_ar_p12_kernel(const bf16_t* __restrict__ x, int x_stride,
+                                                         const bf16_t* __restrict__ W, PackedW pw,
+                                                         void* __restrict__ h, int h_stride, int N, int K,
+                                                         CarArgs ar) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  gemv_block<M, NT, 1, UNROLL, PRO_NONE, EPI_AR, false, WF_P12, 1, TAIL>(blockIdx.x, blockIdx.y, smem, x, x_stride,
+                                                                         nullptr, 0.f, W, h, h_stride, N, K, nullptr, 1,
+                                                                         RopeEpi{}, ar, pw);
+}
+
+// WF_P12 form of the MoE decode GEMVs, pw the twin of the [E * N, K] view of the expert stack W, so row n of
+// expert e is row e * N + n of the twin. M = 1: the pair form (by = (token, slot) pair); M = 2 with
+// EPI_COMBINE: by = token, RPW = M = top-k
+template <int M, int NT, int RPW, int PRO, int EPI>
+__global__ __launch_bounds__(NT) void gemv_moe_p12_kernel(const bf16_t* __restrict__ x, int x_stride,
+                                                          const bf16_t* __restrict__ norm_w, float eps,
+                                                          const bf16_t* __restrict__ W, PackedW pw,
+                                                          void* __restrict__ out, int out_stride, int N, int K,
+                                                          const int32_t* __restrict__ expert_ids, int x_div,
+                                                          RopeEpi rope) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  gemv_block<M, NT, RPW, 4, PRO, EPI, true, WF_P12>(blockIdx.x, blockIdx.y, smem, x, x_stride, norm_w, eps, W, out,
+                                                    out_stride, N, K, expert_ids, x_div, rope, CarArgs{}, pw);
 }
 
 }  // namespace llmc

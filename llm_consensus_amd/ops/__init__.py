@@ -186,6 +186,19 @@ def gemm_plan(M: int, N: int) -> str:
     return ("256x256", "128x192")[kernels().gemm_plan(int(M), int(N))]
 
 
+GEMV_DENSE, GEMV_AR, GEMV_MOE_PAIR, GEMV_MOE_COMBINE = 0, 1, 2, 3   # csrc/kernels/gemv_geom.h GemvOp
+EPI_COMBINE, EPI_AR = 5, 6                                          # the MoE combine's and the fused all-reduce's
+WF_BF16, WF_P13, WF_P12 = 0, 1, 2                                   # weight formats
+
+
+def gemv_plan(op: int, M: int, N: int, K: int, epi: int, wf: int = WF_BF16):
+    """``(nt, rpw, unroll, has_kernel)``: the block the decode GEMV launch ``op`` of ``(M, N, K, epi)`` runs in
+    weight format ``wf`` (threads, rows per wave, 16-B loads per lane in flight; zeros: no such launch) and
+    whether the library holds that kernel, from the rule and lookup the launches use
+    (csrc/kernels/gemv_geom.h, ``llmc_gemv_plan``). No GPU is touched."""
+    return kernels().gemv_plan(int(op), int(M), int(N), int(K), int(epi), int(wf))
+
+
 def gemv(x: torch.Tensor, W: torch.Tensor, epi: int = EPI_BF16, out: Optional[torch.Tensor] = None,
          norm_w: Optional[torch.Tensor] = None, eps: float = 1e-5, mfma: bool = False) -> torch.Tensor:
     """Always the weight-streaming path (M <= 32; the kernel library picks VALU / MFMA form)."""
