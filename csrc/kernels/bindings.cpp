@@ -71,8 +71,12 @@ int llmc_attn_prefill_form(int, int, int, int, int, int, int);
 int llmc_attn_prefill_plan(int, int, int, int, int, int, int, int*);
 int64_t llmc_attn_prefill_counters(int, int, int, int);
 int llmc_sample(const void*, int64_t, int, int, const void*, const void*, const void*, const void*, const void*, void*,
-                void*, void*, void*, void*, void*, const void*, int, int, void*, void*, int, int, hipStream_t);
+                void*, void*, void*, void*, void*, const void*, int, int, void*, void*, int, int, void*, int64_t,
+                const void*, hipStream_t);
 int llmc_sample_parts();
+int llmc_penalize_logits(void*, int64_t, int, int, const void*, int64_t, const void*, const void*, const void*,
+                         hipStream_t);
+int llmc_penalty_seed(void*, int, const void*, int, hipStream_t);
 int llmc_moe_route(const void*, int, int, int, void*, void*, hipStream_t);
 int llmc_moe_down_combine(int, const void*, int, const void*, const void*, const void*, void*, int, int, int, int,
                           hipStream_t);
@@ -309,10 +313,17 @@ PYBIND11_MODULE(_llmc_hip, m) {
   });
   m.def("sample", [](ptr logits, int64_t rs, int B, int V, ptr it, ptr tk, ptr tp, ptr seeds, ptr pos, ptr wv, ptr wi,
                      ptr next, ptr tin, ptr sl, ptr slots, ptr bt, int bts, int bs, ptr ot, ptr oc, int cap,
-                     int use_topkp, ptr s) {
+                     int use_topkp, ptr words, int64_t ws, ptr lmp, ptr s) {
     check(llmc_sample(P(logits), rs, B, V, P(it), P(tk), P(tp), P(seeds), P(pos), P(wv), P(wi), P(next), P(tin), P(sl),
-                      P(slots), P(bt), bts, bs, P(ot), P(oc), cap, use_topkp, S(s)),
+                      P(slots), P(bt), bts, bs, P(ot), P(oc), cap, use_topkp, P(words), ws, P(lmp), S(s)),
           "sample");
+  });
+  m.def("penalize_logits", [](ptr logits, int64_t rs, int B, int V, ptr words, int64_t ws, ptr rep, ptr freq, ptr pres,
+                              ptr s) {
+    check(llmc_penalize_logits(P(logits), rs, B, V, P(words), ws, P(rep), P(freq), P(pres), S(s)), "penalize_logits");
+  });
+  m.def("penalty_seed", [](ptr words_row, int V, ptr ids, int n, ptr s) {
+    check(llmc_penalty_seed(P(words_row), V, P(ids), n, S(s)), "penalty_seed");
   });
   m.def("sample_parts", []() { return llmc_sample_parts(); });
   m.def("moe_route", [](ptr logits, int T, int E, int k, ptr w, ptr ids, ptr s) {

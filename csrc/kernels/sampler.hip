@@ -117,11 +117,22 @@ struct DecodeState {
   int32_t* out_tokens;    // [B, cap]
   int32_t* out_count;     // [B]
   int cap;
+  uint16_t* words;        // [B, words_stride] penalty history words, or null (no row is penalised)
+  int64_t words_stride;
 };
+
+// Penalty history word of one (row, vocabulary id): bit 15 = the id occurs in the context the row was
+// bound with, bits 0-14 = how often the id was generated since, saturating.
+constexpr uint32_t kWordCtx = 0x8000u, kWordCount = 0x7fffu;
 
 // No-op unless tokens_in is given (a bare sample call must not move the position/step counter).
 __device__ __forceinline__ void advance(const DecodeState& st, int b, int tok) {
   if (st.tokens_in == nullptr) return;
+  if (st.words != nullptr) {
+    uint16_t* w = st.words + b * st.words_stride + tok;
+    const uint32_t x = *w;
+    if ((x & kWordCount) != kWordCount) *w = static_cast<uint16_t>(x + 1);
+  }
   if (st.out_tokens != nullptr) {
     const int cnt = st.out_count[b];
     if (cnt < st.cap) st.out_tokens[static_cast<int64_t>(b) * st.cap + cnt] = tok;
@@ -169,6 +180,7 @@ __global__ __launch_bounds__(kTKThreads) void sample_topkp_kernel(const float* _
                                                                   const int* __restrict__ top_k,
                                                                   const float* __restrict__ top_p,
                                                                   const int64_t* __restrict__ seeds,
+                                                                  const float* __restrict__ ln_min_p,
                                                                   int32_t* __restrict__ next, DecodeState st) {
   const int b = blockIdx.x;
   const float* row = logits + b * row_stride;
@@ -271,11 +283,16 @@ __global__ __launch_bounds__(kTKThreads) void sample_topkp_kernel(const float* _
     thr = max(thr, sh_prefix);
   }
   // ---- Gumbel-max over survivors ----
+  // min-p (sampled rows, after top-k / top-p): keep l iff (l - mx) * it >= ln(min_p); the row maximum
+  // always survives (mx = +inf would make its own difference NaN). -inf, or no array: off.
+  const float lmp = (ln_min_p != nullptr && !greedy) ? ln_min_p[b] : -INFINITY;
+  const bool minp = lmp > -INFINITY;
   float bv = -INFINITY;
   int bi = 0x7fffffff;
   for (int i = threadIdx.x; i < V; i += kTKThreads) {
     const float l = row[i];
     if (fkey(l) < thr) continue;
+    if (minp && !(l == mx || (l - mx) * it >= lmp)) continue;
     const float v = greedy ? l : l * it + gumbel(key, static_cast<uint32_t>(i), step);
     argmax_merge(bv, bi, v, i);
   }
@@ -293,15 +310,76 @@ __global__ __launch_bounds__(kTKThreads) void sample_topkp_kernel(const float* _
   }
 }
 
+// ------------------------------------------------------------------------------------------
+// Sampling penalties, a launch of their own ahead of the sampler kernels (which walk the row up to
+// eleven times: reading the words there would cost more than this one pass). In place, float32:
+//   word != 0 (context or generated id):  l = l > 0 ? l / r : l * r      (repetition penalty)
+//   count c > 0 (generated ids only):     l = fmaf(-f, c, l) - p          (frequency, presence)
+// Ids whose word is 0 and rows whose three parameters are neutral are not written.
+// grid (kParts, B), 256 threads, the partition of sample_stage1_kernel
+__global__ __launch_bounds__(256) void penalize_logits_kernel(float* __restrict__ logits, int64_t row_stride, int V,
+                                                              const uint16_t* __restrict__ words,
+                                                              int64_t words_stride, const float* __restrict__ rep,
+                                                              const float* __restrict__ freq,
+                                                              const float* __restrict__ pres) {
+  const int p = blockIdx.x, b = blockIdx.y;
+  const float r = rep[b], f = freq[b], pp = pres[b];
+  if (r == 1.f && f == 0.f && pp == 0.f) return;
+  float* row = logits + b * row_stride;
+  const uint16_t* wrow = words + b * words_stride;
+  const int per = (V + kParts - 1) / kParts;
+  const int lo = p * per, hi = min(V, lo + per);
+  for (int i = lo + threadIdx.x; i < hi; i += 256) {
+    const uint32_t w = wrow[i];
+    if (w == 0) continue;
+    float l = row[i];
+    l = (l > 0.f) ? l / r : l * r;
+    const uint32_t c = w & kWordCount;
+    if (c > 0) {
+      l = fmaf(-f, static_cast<float>(c), l);
+      l = l - pp;
+    }
+    row[i] = l;
+  }
+}
+
+// Marks the context bit of ids[0..n) in one row of words the caller zeroed before (zeroing here would
+// race the marks of other blocks). Every mark stores the same constant, so duplicates are benign;
+// ids outside [0, V) are skipped.
+__global__ __launch_bounds__(256) void penalty_seed_kernel(uint16_t* __restrict__ wrow, int V,
+                                                           const int32_t* __restrict__ ids, int n) {
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= n) return;
+  const int id = ids[j];
+  if (id >= 0 && id < V) wrow[id] = static_cast<uint16_t>(kWordCtx);
+}
+
 }  // namespace llmc
 
 using namespace llmc;
+
+extern "C" int llmc_penalize_logits(void* logits, int64_t row_stride, int B, int V, const void* words,
+                                    int64_t words_stride, const void* rep, const void* freq, const void* pres,
+                                    hipStream_t s) {
+  if (B <= 0 || V <= 0) return 0;
+  penalize_logits_kernel<<<dim3(kParts, B), 256, 0, s>>>((float*)logits, row_stride, V, (const uint16_t*)words,
+                                                         words_stride, (const float*)rep, (const float*)freq,
+                                                         (const float*)pres);
+  return static_cast<int>(hipGetLastError());
+}
+
+extern "C" int llmc_penalty_seed(void* words_row, int V, const void* ids, int n, hipStream_t s) {
+  if (n <= 0 || V <= 0) return 0;
+  penalty_seed_kernel<<<(n + 255) / 256, 256, 0, s>>>((uint16_t*)words_row, V, (const int32_t*)ids, n);
+  return static_cast<int>(hipGetLastError());
+}
 
 extern "C" int llmc_sample(const void* logits, int64_t row_stride, int B, int V, const void* inv_temp,
                            const void* top_k, const void* top_p, const void* seeds, const void* positions,
                            void* workspace_v, void* workspace_i, void* next, void* tokens_in, void* seq_lens,
                            void* slots, const void* block_tables, int bt_stride, int bs, void* out_tokens,
-                           void* out_count, int cap, int use_topkp, hipStream_t s) {
+                           void* out_count, int cap, int use_topkp, void* words, int64_t words_stride,
+                           const void* ln_min_p, hipStream_t s) {
   DecodeState st;
   st.tokens_in = (int32_t*)tokens_in;
   st.positions = (int32_t*)positions;
@@ -313,10 +391,12 @@ extern "C" int llmc_sample(const void* logits, int64_t row_stride, int B, int V,
   st.out_tokens = (int32_t*)out_tokens;
   st.out_count = (int32_t*)out_count;
   st.cap = cap;
+  st.words = (uint16_t*)words;
+  st.words_stride = words_stride;
   if (use_topkp) {
     sample_topkp_kernel<<<B, kTKThreads, 0, s>>>((const float*)logits, row_stride, V, (const float*)inv_temp,
                                                  (const int*)top_k, (const float*)top_p, (const int64_t*)seeds,
-                                                 (int32_t*)next, st);
+                                                 (const float*)ln_min_p, (int32_t*)next, st);
     return static_cast<int>(hipGetLastError());
   }
   sample_stage1_kernel<<<dim3(kParts, B), 256, 0, s>>>((const float*)logits, row_stride, V, (const float*)inv_temp,

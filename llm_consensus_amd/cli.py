@@ -6,7 +6,8 @@ entry and the judge must resolve, main.go:395-415) → fan-out → judge → per
 "Providers" are local engines on the node's GPUs (``provider/local.py``) or the CPU stub.
 
 Extra engine flags (no reference counterpart): ``--max-tokens``,
-``--temperature``, ``--top-p``, ``--top-k``, ``--seed``, ``--gpus``, ``--trace``,
+``--temperature``, ``--top-p``, ``--top-k``, ``--seed``, ``--min-p``, ``--repetition-penalty``,
+``--presence-penalty``, ``--frequency-penalty``, ``--model-sampling``, ``--gpus``, ``--trace``,
 ``--list-models``, ``--weights-dir`` (Hugging Face checkpoints as extra local model families),
 ``--placement`` (pin models / TP groups to GPUs).
 """
@@ -28,7 +29,7 @@ from .consensus import Judge, prompt_header, response_block
 from .context import Context
 from .flags import FlagSet, parse_or_exit
 from .output import Result, encode_result
-from .provider.base import Request
+from .provider.base import Request, check_sampling
 from .provider.registry import Registry
 from .runner import Callbacks, Runner
 from .utils.gostr import trim_space
@@ -65,6 +66,11 @@ class Config:
     judge_tp: int = 0
     server: str = ""
     judge_explicit: bool = True
+    min_p: float = 0.0
+    repetition_penalty: float = 1.0
+    presence_penalty: float = 0.0
+    frequency_penalty: float = 0.0
+    model_sampling: bool = False
 
 
 def make_flagset() -> FlagSet:
@@ -86,6 +92,12 @@ def make_flagset() -> FlagSet:
     fs.add("top-p", "float", 1.0, "Nucleus sampling mass")
     fs.add("top-k", "int", 0, "Top-k sampling (0 = off)")
     fs.add("seed", "int", 0, "Sampling seed (0 = derived from the model name)")
+    fs.add("min-p", "float", 0.0, "Drop tokens less likely than min-p x the most likely one (0 = off)")
+    fs.add("repetition-penalty", "float", 1.0, "Divide / multiply the logits of ids in the context or generated (1 = off)")
+    fs.add("presence-penalty", "float", 0.0, "Subtracted from the logits of generated ids")
+    fs.add("frequency-penalty", "float", 0.0, "Subtracted from the logits of generated ids, times their count")
+    fs.add("model-sampling", "bool", False,
+           "Checkpoint models sample with their generation_config.json values where a flag is left neutral")
     fs.add("gpus", "string", "", "Comma-separated GPU ids to place models on (default: all visible)")
     fs.add("trace", "bool", False, "Write a Chrome trace of engine spans to the run directory")
     fs.add("placement", "string", "",
@@ -159,6 +171,14 @@ def _go_path_err(op: str, path: str, e: OSError) -> str:
 def parse_flags(argv: List[str], stdout: TextIO = sys.stdout, stderr: TextIO = sys.stderr, stdin=None) -> Config:
     fs = make_flagset()
     v, rest = parse_or_exit(fs, argv, stderr)
+    for name in ("min_p", "repetition_penalty", "presence_penalty", "frequency_penalty"):
+        try:
+            check_sampling(**{name: v[name]})
+        except ValueError as e:  # like any bad flag value: the error, the usage, exit 2
+            flag = name.replace("_", "-")
+            stderr.write(f'invalid value "{_go_num(v[name])}" for flag -{flag}: {str(e).split(": ", 1)[1]}\n{fs.usage()}')
+            stderr.flush()
+            raise SystemExit(2)
     wd = v["weights_dir"] or os.environ.get("LLMC_WEIGHTS_DIR", "")
     if wd:
         register_weights(wd)
@@ -177,7 +197,9 @@ def parse_flags(argv: List[str], stdout: TextIO = sys.stdout, stderr: TextIO = s
                  max_tokens=v["max_tokens"], temperature=v["temperature"], top_p=v["top_p"], top_k=v["top_k"],
                  seed=v["seed"], gpus=v["gpus"], trace=v["trace"], placement=v["placement"],
                  judge_tp=v["judge_tp"], server=v["server"] or os.environ.get("LLMC_SERVER", ""),
-                 judge_explicit=any(a.lstrip("-").split("=")[0] == "judge" for a in argv[:len(argv) - len(rest)]))
+                 judge_explicit=any(a.lstrip("-").split("=")[0] == "judge" for a in argv[:len(argv) - len(rest)]),
+                 min_p=v["min_p"], repetition_penalty=v["repetition_penalty"], presence_penalty=v["presence_penalty"],
+                 frequency_penalty=v["frequency_penalty"], model_sampling=v["model_sampling"])
     cfg.prompt = get_prompt(rest, cfg.file, stdin)
     return cfg
 
@@ -219,7 +241,8 @@ def init_registry(cfg: Config, concurrency: int = 1) -> Registry:
 
             pins = parse_pins(cfg.placement) if cfg.placement else None
             backend = LocalBackend(local_specs, judge=cfg.judge, gpus=gpus, trace=cfg.trace, counts=counts,
-                                   pins=pins, judge_tp=cfg.judge_tp, concurrency=concurrency)
+                                   pins=pins, judge_tp=cfg.judge_tp, concurrency=concurrency,
+                                   sampling=_request_template(cfg), model_sampling=cfg.model_sampling)
         except Exception as e:  # noqa: BLE001
             raise CLIError(f"initializing provider for {local_specs[0].name}: {e}") from None
         for spec in local_specs:
@@ -257,7 +280,14 @@ def run(argv: List[str], stdout: TextIO = sys.stdout, stderr: TextIO = sys.stder
 
 def _request_template(cfg: Config) -> Request:
     return Request(model="", prompt="", max_tokens=cfg.max_tokens or None, temperature=cfg.temperature,
-                   top_p=cfg.top_p, top_k=cfg.top_k or None, seed=cfg.seed or None)
+                   top_p=cfg.top_p, top_k=cfg.top_k or None, seed=cfg.seed or None, min_p=cfg.min_p,
+                   repetition_penalty=cfg.repetition_penalty, presence_penalty=cfg.presence_penalty,
+                   frequency_penalty=cfg.frequency_penalty)
+
+
+def _go_num(v) -> str:
+    r = repr(float(v))
+    return r[:-2] if r.endswith(".0") else r
 
 
 def _run_with_registry(cfg: Config, registry: Registry, ctx: Context, show_ui: bool, start: float,
@@ -405,7 +435,9 @@ def _run_remote(cfg: Config, ctx: Context, show_ui: bool, stderr: TextIO) -> Res
     u = urllib.parse.urlsplit(cfg.server if "://" in cfg.server else "http://" + cfg.server)
     body = {"prompt": cfg.prompt, "models": cfg.models, "timeout": cfg.timeout, "stream": True,
             "max_tokens": cfg.max_tokens or None, "temperature": cfg.temperature, "top_p": cfg.top_p,
-            "top_k": cfg.top_k or None, "seed": cfg.seed or None}
+            "top_k": cfg.top_k or None, "seed": cfg.seed or None, "min_p": cfg.min_p,
+            "repetition_penalty": cfg.repetition_penalty, "presence_penalty": cfg.presence_penalty,
+            "frequency_penalty": cfg.frequency_penalty}
     if cfg.judge_explicit:
         body["judge"] = cfg.judge
     conn_cls = http.client.HTTPSConnection if u.scheme == "https" else http.client.HTTPConnection

@@ -23,7 +23,6 @@ from typing import Callable, List, Optional
 
 import torch
 
-from .. import ops
 from .engine import Engine, EngineError, SamplingParams, Sequence
 
 TokenFn = Callable[["Row", List[int]], None]
@@ -60,7 +59,7 @@ class ContinuousBatcher:
         self._eos = set(engine.cfg.eos)
         e = engine
         self._row_state = [e.tokens_in, e.positions, e.seq_lens, e.slots, e.block_tables, e.out_tokens,
-                           e.out_count, e.next_tok, e.inv_temp, e.top_k, e.top_p, e.seeds]
+                           e.out_count, e.next_tok, e.inv_temp, e.top_k, e.top_p, e.seeds, e.ln_min_p]
 
     @property
     def free_rows(self) -> int:
@@ -83,18 +82,11 @@ class ContinuousBatcher:
         with e._on_stream():
             e.block_tables[r:r + 1].copy_(e._block_table([seq]))
             e.logits_local[r].copy_(seq.logits)
-            e.inv_temp[r] = 0.0 if params.temperature <= 0 else 1.0 / params.temperature
-            e.top_k[r] = params.top_k
-            e.top_p[r] = params.top_p
-            e.seeds[r] = params.seed
+            e._bind_sampling(r, seq, params)  # a penalised row: its history words zeroed and seeded
             e.positions[r] = seq.length - 1
             e.out_count[r] = 0
-            sl = slice(r, r + 1)
-            ops.sample(e.logits_local[sl], e.inv_temp[sl], e.top_k[sl], e.top_p[sl], e.seeds[sl], e.positions[sl],
-                       e.next_tok[sl], e.ws_v[sl] if e.ws_v is not None else None,
-                       e.ws_i[sl] if e.ws_i is not None else None, tokens_in=e.tokens_in[sl], seq_lens=e.seq_lens[sl],
-                       slots=e.slots[sl], block_tables=e.block_tables[sl], bs=e.bs, out_tokens=e.out_tokens[sl],
-                       out_count=e.out_count[sl], use_topkp=params.top_k > 0 or params.top_p < 1.0)
+            e._use_topkp, e._use_penalties = params.topkp, params.penalised
+            e._sample(1, e.logits_local[r:r + 1], r0=r)
         seq.row = r
         row = Row(seq, params, tag, ctx)
         self.rows.append(row)
@@ -130,6 +122,11 @@ class ContinuousBatcher:
             if stop or n >= p.max_tokens:
                 row.done = True
 
+    def _penalty_state(self) -> list:
+        """The rows' penalty history words and parameters, once the engine holds them."""
+        e = self.e
+        return [] if e.pen_words is None else [e.pen_words, e.pen_rep, e.pen_freq, e.pen_pres]
+
     def _compact(self) -> List[Row]:
         """Drop finished rows; the live rows behind them move down (device row copies)."""
         keep = [r for r in self.rows if not r.done]
@@ -140,12 +137,13 @@ class ContinuousBatcher:
             for t, row in enumerate(keep):
                 s = row.seq.row
                 if s != t:
-                    for buf in self._row_state:
+                    for buf in self._row_state + self._penalty_state():
                         buf[t].copy_(buf[s])
                     row.seq.row = t
         self.rows = keep
         for row in gone:
             row.seq.length = row.base + len(row.tokens)
+            row.seq.ids[row.base:] = row.tokens
             row.seq.has_logits = False
             row.seq.row = -1
         return gone
@@ -161,7 +159,8 @@ class ContinuousBatcher:
         with e._on_stream():
             if need and B:
                 bucket = e._bucket(max(r.base + r.issued for r in self.rows) + S + 1)
-                e._use_topkp = any(r.params.top_k > 0 or r.params.top_p < 1.0 for r in self.rows)
+                e._use_topkp = any(r.params.topkp for r in self.rows)
+                e._use_penalties = any(r.params.penalised for r in self.rows)
                 graph = e._graph(B, bucket) if (e.on_gpu and e.ecfg.use_graphs) else None
                 if graph is not None:
                     graph.replay()

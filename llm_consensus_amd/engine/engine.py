@@ -208,6 +208,26 @@ class SamplingParams:
     top_k: int = 0
     seed: int = 0
     stop_on_eos: bool = True
+    # sampled rows keep a token only if its probability is >= min_p x the most likely token's (0 = off)
+    min_p: float = 0.0
+    # over the ids of the context and the ids generated so far: l = l > 0 ? l / r : l * r (1 = off)
+    repetition_penalty: float = 1.0
+    # over the ids generated so far: l -= presence_penalty + frequency_penalty x (times generated)
+    presence_penalty: float = 0.0
+    frequency_penalty: float = 0.0
+
+    @property
+    def penalised(self) -> bool:
+        return self.repetition_penalty != 1.0 or self.presence_penalty != 0.0 or self.frequency_penalty != 0.0
+
+    @property
+    def topkp(self) -> bool:
+        """Whether the row needs the top-k/top-p launch (which also applies min-p)."""
+        return self.top_k > 0 or self.top_p < 1.0 or self.min_p > 0.0
+
+    @property
+    def ln_min_p(self) -> float:
+        return math.log(self.min_p) if self.min_p > 0.0 else float("-inf")
 
 
 class Sequence:
@@ -218,6 +238,7 @@ class Sequence:
         self.row = -1
         self.blocks: List[int] = []
         self.length = 0
+        self.ids: List[int] = []  # the tokens it holds (host copy): the context of the sampling penalties
         self.has_logits = False
         self.logits: Optional[torch.Tensor] = None  # last-token logits [V_local] after prefill
 
@@ -368,6 +389,12 @@ class Engine:
         self.top_k = torch.zeros(B, **i32)
         self.top_p = torch.ones(B, dtype=torch.float32, device=dev)
         self.seeds = torch.zeros(B, dtype=torch.int64, device=dev)
+        # log(min_p) per row for the top-k/top-p launch (-inf = off)
+        self.ln_min_p = torch.full((B,), float("-inf"), dtype=torch.float32, device=dev)
+        # sampling penalties: history words [B, V] and the rows' parameters, allocated by the first
+        # penalised bind (_penalty_state); an engine that never sees a penalty never holds them
+        self.pen_words: Optional[torch.Tensor] = None
+        self.pen_rep = self.pen_freq = self.pen_pres = None
         bf = dict(dtype=torch.bfloat16, device=dev)
         self.h = torch.zeros(B, c.hidden, **bf)
         self.q = torch.zeros(B, self.w.q_size, **bf)
@@ -467,6 +494,7 @@ class Engine:
             self.alloc.free(seq.blocks)
             seq.blocks = []
         seq.length = 0
+        seq.ids = []
         seq.logits = None
         seq.has_logits = False
 
@@ -476,6 +504,7 @@ class Engine:
         if not 0 <= length <= seq.length:
             raise EngineError(f"truncate to {length} of a {seq.length}-token sequence")
         seq.length = length
+        del seq.ids[length:]
         seq.logits = None
         seq.has_logits = False
 
@@ -533,6 +562,7 @@ class Engine:
                 pos.append(p)
                 slots.append(s.blocks[p // self.bs] * self.bs + p % self.bs)
             s.length += len(toks)
+            s.ids.extend(toks)
             ctx_lens.append(s.length)
         T = len(ids)
         i32 = dict(dtype=torch.int32)
@@ -839,7 +869,7 @@ class Engine:
             with self._on_stream():
                 self.prefill([seq], [list(prompt)])
                 self._reserve(seq, seq.length + 4)
-                self._use_topkp = False
+                self._use_topkp = self._use_penalties = False
                 self._bind_rows([seq], [SamplingParams(2, 0.0, 1.0, 0, 0, False)])
                 self._sample(1, self._gather_logits(1))  # the prefill's token -> this step's input
                 pos = int(self.positions[0].item())
@@ -860,7 +890,11 @@ class Engine:
         ops.linear(self.h[:B], self.w.lm_head, EPI_F32, out=lg, norm_w=self.w.final_norm, eps=self.cfg.rms_eps,
                    mfma=self.mfma_decode, Wp=self.w.p_lm_head if self.packed else None)
         logits = self._gather_logits(B)
+        if self._debug_raw_logits is not None:  # eager debug steps only: the row before any penalty
+            self._debug_raw_logits.append(logits.clone())
         self._sample(B, logits)
+
+    _debug_raw_logits: Optional[list] = None
 
     def _moe_decode(self, h, Lw, B, routed: bool = False) -> None:
         """``routed``: the fused attention + o_proj launch already wrote moe_w / moe_ids."""
@@ -934,13 +968,56 @@ class Engine:
             torch.cuda.current_stream(self.device).wait_stream(self.stream)
         return out
 
-    def _sample(self, B: int, logits: torch.Tensor) -> None:
+    def _sample(self, B: int, logits: torch.Tensor, r0: int = 0) -> None:
+        """Sample rows r0 .. r0 + B - 1 from ``logits`` [B, V] and advance their state. With
+        ``_use_penalties`` the rows are penalised first from their history words (a launch of its
+        own) and the advance counts the sampled ids there; every rank of a TP group holds the full
+        table and penalises the gathered row, so the ranks sample the same token and stay equal."""
         use_topkp = bool(self._use_topkp)
-        ops.sample(logits, self.inv_temp[:B], self.top_k[:B], self.top_p[:B], self.seeds[:B], self.positions[:B],
-                   self.next_tok[:B], self.ws_v[:B] if self.ws_v is not None else None,
-                   self.ws_i[:B] if self.ws_i is not None else None, tokens_in=self.tokens_in[:B],
-                   seq_lens=self.seq_lens[:B], slots=self.slots[:B], block_tables=self.block_tables[:B], bs=self.bs,
-                   out_tokens=self.out_tokens[:B], out_count=self.out_count[:B], use_topkp=use_topkp)
+        sl = slice(r0, r0 + B)
+        pen = {}
+        if self._use_penalties:
+            pen = dict(words=self.pen_words[sl], rep=self.pen_rep[sl], freq=self.pen_freq[sl], pres=self.pen_pres[sl])
+        ops.sample(logits, self.inv_temp[sl], self.top_k[sl], self.top_p[sl], self.seeds[sl], self.positions[sl],
+                   self.next_tok[sl], self.ws_v[sl] if self.ws_v is not None else None,
+                   self.ws_i[sl] if self.ws_i is not None else None, tokens_in=self.tokens_in[sl],
+                   seq_lens=self.seq_lens[sl], slots=self.slots[sl], block_tables=self.block_tables[sl], bs=self.bs,
+                   out_tokens=self.out_tokens[sl], out_count=self.out_count[sl], use_topkp=use_topkp,
+                   ln_min_p=self.ln_min_p[sl], **pen)
+
+    _use_penalties = False
+
+    def _penalty_state(self) -> None:
+        """Allocate the penalty history words and parameters (first penalised bind)."""
+        if self.pen_words is not None:
+            return
+        B, dev = self.ecfg.max_batch, self.device
+        self.pen_words = torch.zeros(B, self.cfg.vocab, dtype=torch.int16, device=dev)
+        self.pen_rep = torch.ones(B, dtype=torch.float32, device=dev)
+        self.pen_freq = torch.zeros(B, dtype=torch.float32, device=dev)
+        self.pen_pres = torch.zeros(B, dtype=torch.float32, device=dev)
+
+    def _bind_sampling(self, r: int, s: "Sequence", p: SamplingParams) -> None:
+        """Sampling state of decode row ``r``. A penalised row's history words start from zero with
+        the context bit of every id the sequence holds: a sequence bound again (a judge session, an
+        incremental prefill) counts its earlier output as context."""
+        self.inv_temp[r] = 0.0 if p.temperature <= 0 else 1.0 / p.temperature
+        self.top_k[r] = p.top_k
+        self.top_p[r] = p.top_p
+        self.seeds[r] = p.seed
+        self.ln_min_p[r] = p.ln_min_p
+        if p.penalised:
+            assert len(s.ids) == s.length, (len(s.ids), s.length)
+            self._penalty_state()
+        if self.pen_words is None:
+            return
+        self.pen_rep[r] = p.repetition_penalty
+        self.pen_freq[r] = p.frequency_penalty
+        self.pen_pres[r] = p.presence_penalty
+        if p.penalised:
+            self.pen_words[r].zero_()
+            ids = torch.tensor(s.ids, dtype=torch.int32)
+            ops.penalty_seed(self.pen_words[r], ids.to(self.device, non_blocking=True) if self.on_gpu else ids)
 
     def _bucket(self, ctx_tokens: int) -> int:
         """Smallest attention bucket covering ``ctx_tokens`` (so a short context's graph does not
@@ -954,13 +1031,19 @@ class Engine:
         return list(range(len(self.attn_buckets)))
 
     @torch.no_grad()
-    def warmup_graphs(self, batch_sizes: Optional[List[int]] = None, topkp: bool = False) -> int:
+    def warmup_graphs(self, batch_sizes: Optional[List[int]] = None, topkp: bool = False,
+                      penalties: bool = False) -> int:
         """Capture every decode graph this engine can need (per batch size x context bucket) up
         front. A process hosting several engines must do this before serving: a capture running
         beside another engine's work is invalidated by HIP, so serving never captures
-        (``capture_on_demand`` False -> a missing graph runs eagerly)."""
+        (``capture_on_demand`` False -> a missing graph runs eagerly). ``topkp`` / ``penalties``:
+        the sampling form the graphs carry (the top-k/top-p launch; the penalty launch ahead of the
+        sampler); call once per form the process will serve."""
         if not (self.on_gpu and self.ecfg.use_graphs):
             return 0
+        if penalties:
+            self._penalty_state()
+        self.capture_on_demand = True
         n = 0
         # TP: every rank starts its warm-up steps (eager, with collectives) together — a rank still
         # warming another engine would otherwise hold its peers' spins past their 1-s bound — and
@@ -969,10 +1052,10 @@ class Engine:
         with self._on_stream():
             for B in batch_sizes or list(range(1, self.ecfg.max_batch + 1)):
                 for bk in self.buckets():
-                    self._use_topkp = topkp
+                    self._use_topkp, self._use_penalties = topkp, penalties
                     self._graph(B, bk)
                     n += 1
-        self._use_topkp = False
+        self._use_topkp = self._use_penalties = False
         self.capture_on_demand = False
         if self.tp.size > 1:
             self.stream.synchronize()
@@ -982,16 +1065,16 @@ class Engine:
     capture_on_demand = True
 
     def _graph(self, B: int, bucket: int):
-        key = (B, self._use_topkp, bucket)
+        key = (B, bool(self._use_topkp), bool(self._use_penalties), bucket)
         g = self._graphs.get(key)
         if g is not None or not self.capture_on_demand:
             return g
         S = self.ecfg.steps_per_graph
         # warm up once eagerly (kernel attributes, lazy module state) with the device state
         # snapshotted and restored, then capture S steps.
-        snap = self._snapshot_state()
+        snap = self._snapshot_state(B)
         self._decode_step(B, bucket)
-        self._restore_state(snap)
+        self._restore_state(snap, B)
         self.stream.synchronize()
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g, stream=self.stream, capture_error_mode="thread_local"):
@@ -1002,13 +1085,18 @@ class Engine:
 
     _use_topkp = False
 
-    def _snapshot_state(self):
-        return [t.clone() for t in (self.tokens_in, self.positions, self.seq_lens, self.slots, self.out_tokens,
-                                    self.out_count, self.next_tok)]
+    def _state_tensors(self, B: int):
+        st = [self.tokens_in, self.positions, self.seq_lens, self.slots, self.out_tokens, self.out_count,
+              self.next_tok]
+        if self._use_penalties:  # the eager warm-up step before a capture counts its tokens there
+            st.append(self.pen_words[:B])
+        return st
 
-    def _restore_state(self, snap) -> None:
-        for dst, src in zip((self.tokens_in, self.positions, self.seq_lens, self.slots, self.out_tokens,
-                             self.out_count, self.next_tok), snap):
+    def _snapshot_state(self, B: int):
+        return [t.clone() for t in self._state_tensors(B)]
+
+    def _restore_state(self, snap, B: int) -> None:
+        for dst, src in zip(self._state_tensors(B), snap):
             dst.copy_(src)
 
     @torch.no_grad()
@@ -1024,7 +1112,8 @@ class Engine:
         eos_set = set(self.cfg.eos)
         with self._on_stream(), trace.span("decode", engine=self.name, rows=B):
             max_new = max(p.max_tokens for p in params)
-            self._use_topkp = any((p.top_k > 0 or p.top_p < 1.0) for p in params)
+            self._use_topkp = any(p.topkp for p in params)
+            self._use_penalties = any(p.penalised for p in params)
             for i, (s, p) in enumerate(zip(seqs, params)):
                 if not s.has_logits:
                     raise EngineError("sequence has no prefill logits")
@@ -1295,10 +1384,7 @@ class Engine:
         for i, (s, p) in enumerate(zip(seqs, params)):
             s.row = i
             self.logits_local[i].copy_(s.logits)
-            self.inv_temp[i] = 0.0 if p.temperature <= 0 else 1.0 / p.temperature
-            self.top_k[i] = p.top_k
-            self.top_p[i] = p.top_p
-            self.seeds[i] = p.seed
+            self._bind_sampling(i, s, p)
             self.positions[i] = s.length - 1
             self.out_count[i] = 0
 
@@ -1311,9 +1397,12 @@ class Engine:
         return toks[0], lg[0]
 
     @torch.no_grad()
-    def debug_decode_logits_batch(self, prompts: List[Seq[int]], n: int):
+    def debug_decode_logits_batch(self, prompts: List[Seq[int]], n: int,
+                                  params: Optional[List[SamplingParams]] = None):
         """``debug_decode_logits`` for B = len(prompts) rows decoded together (the batched decode
-        GEMV forms: VALU rows <= 2, MFMA 3-32): (tokens [B][n], logits [B, n, V] f32)."""
+        GEMV forms: VALU rows <= 2, MFMA 3-32): (tokens [B][n], logits [B, n, V] f32). ``params``
+        (default: greedy) samples the rows as ``decode`` would; the logits returned are the raw
+        ones, before any penalty."""
         if self.tp.size != 1:
             raise EngineError("debug_decode_logits: TP=1 only")
         B = len(prompts)
@@ -1325,14 +1414,18 @@ class Engine:
                 self.prefill(seqs, [list(p) for p in prompts])
                 for s in seqs:
                     self._reserve(s, s.length + n + 2)
-                self._use_topkp = False
-                self._bind_rows(seqs, [SamplingParams(n, 0.0, 1.0, 0, 0, False)] * B)
-                rows = [self.logits_local[:B].clone()]
-                self._sample(B, self._gather_logits(B))
-                bucket = self._bucket(max(s.length for s in seqs) + n + 2)
-                for _ in range(n - 1):
-                    self._decode_step(B, bucket)
-                    rows.append(self.logits_local[:B].clone())
+                params = params or [SamplingParams(n, 0.0, 1.0, 0, 0, False)] * B
+                self._use_topkp = any(p.topkp for p in params)
+                self._use_penalties = any(p.penalised for p in params)
+                self._bind_rows(seqs, params)
+                rows = self._debug_raw_logits = [self.logits_local[:B].clone()]
+                try:
+                    self._sample(B, self._gather_logits(B))
+                    bucket = self._bucket(max(s.length for s in seqs) + n + 2)
+                    for _ in range(n - 1):
+                        self._decode_step(B, bucket)
+                finally:
+                    self._debug_raw_logits = None
                 toks = self.out_tokens[:B, :n].clone()
             if self.on_gpu:
                 self.stream.synchronize()
@@ -1344,6 +1437,7 @@ class Engine:
     def _finish(self, seqs, results) -> None:
         for s, r in zip(seqs, results):
             s.length += len(r)
+            s.ids.extend(r)
             s.has_logits = False
 
     def _eos_id(self) -> int:
@@ -1353,11 +1447,14 @@ class Engine:
     @torch.no_grad()
     def generate_ids(self, prompt: Seq[int], max_tokens: int, temperature: float = 1.0, top_p: float = 1.0,
                      top_k: int = 0, seed: int = 0, stop_on_eos: bool = True, ctx: Optional[Context] = None,
-                     on_tokens: Optional[Callable[[List[int]], None]] = None) -> List[int]:
+                     on_tokens: Optional[Callable[[List[int]], None]] = None, min_p: float = 0.0,
+                     repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
+                     frequency_penalty: float = 0.0) -> List[int]:
         seq = self.new_sequence()
         try:
             self.prefill([seq], [list(prompt)])
-            p = SamplingParams(max_tokens, temperature, top_p, top_k, seed, stop_on_eos)
+            p = SamplingParams(max_tokens, temperature, top_p, top_k, seed, stop_on_eos, min_p, repetition_penalty,
+                               presence_penalty, frequency_penalty)
             cb = (lambda i, ids: on_tokens(ids)) if on_tokens else None
             return self.decode([seq], [p], ctx, cb)[0]
         finally:

@@ -32,7 +32,7 @@ from typing import Dict, List, Optional
 
 import torch
 
-from .config import FAMILIES, ModelConfig, RopeScaling
+from .config import FAMILIES, ModelConfig, RopeScaling, SamplingDefaults
 
 
 class CheckpointError(Exception):
@@ -107,8 +107,11 @@ def config_from_hf(path: str, name: Optional[str] = None) -> ModelConfig:
                               int(rs_cfg.get("original_max_position_embeddings", 8192)))
     bos, eos = _ids(hc.get("bos_token_id")), _ids(hc.get("eos_token_id"))
     gen = os.path.join(path, "generation_config.json")
+    sampling = None
     if os.path.isfile(gen):
-        eos = _ids(_read_json(gen).get("eos_token_id")) or eos
+        gc = _read_json(gen)
+        eos = _ids(gc.get("eos_token_id")) or eos
+        sampling = _sampling_defaults(gc, path)
     vocab = int(hc["vocab_size"])
     return ModelConfig(
         name=name or os.path.basename(os.path.normpath(path)),
@@ -134,7 +137,22 @@ def config_from_hf(path: str, name: Optional[str] = None) -> ModelConfig:
         sliding_window=window,
         qkv_bias=mt == "qwen2",
         qk_norm=mt == "qwen3",
+        sampling=sampling,
     )
+
+
+def _sampling_defaults(gc: dict, path: str) -> Optional[SamplingDefaults]:
+    """temperature / top_k / top_p / min_p / repetition_penalty of a generation_config.json (the
+    keys it has; ``None`` if it has none of them)."""
+    kinds = {"temperature": float, "top_k": int, "top_p": float, "min_p": float, "repetition_penalty": float}
+    got = {}
+    for k, typ in kinds.items():
+        if gc.get(k) is not None:
+            try:
+                got[k] = typ(gc[k])
+            except (TypeError, ValueError):
+                raise CheckpointError(f"{path}: generation_config.json: {k} = {gc[k]!r} is not a number") from None
+    return SamplingDefaults(**got) if got else None
 
 
 def register_dir(root: str) -> List[str]:

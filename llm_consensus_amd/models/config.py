@@ -22,6 +22,18 @@ class RopeScaling:
 
 
 @dataclasses.dataclass(frozen=True)
+class SamplingDefaults:
+    """The sampling a checkpoint's ``generation_config.json`` asks for; used only on request
+    (``--model-sampling``), for the knobs a request leaves neutral. The defaults here ARE neutral."""
+
+    temperature: float = 1.0
+    top_k: int = 0
+    top_p: float = 1.0
+    min_p: float = 0.0
+    repetition_penalty: float = 1.0
+
+
+@dataclasses.dataclass(frozen=True)
 class ModelConfig:
     name: str
     arch: str  # "llama" (also Mistral, Qwen2, Qwen3: the same layer layout) | "mixtral" | "phi3"
@@ -54,6 +66,8 @@ class ModelConfig:
     # before the rotation (Qwen3; weights [head_dim], one vector for the layer's q heads, one for
     # its k heads)
     qk_norm: bool = False
+    # generation_config.json's sampling values (checkpoints only; see SamplingDefaults)
+    sampling: Optional[SamplingDefaults] = None
 
     @property
     def eos(self) -> tuple:

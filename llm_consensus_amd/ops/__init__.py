@@ -672,21 +672,86 @@ def sample_parts() -> int:
     return kernels().sample_parts()
 
 
+def _words_check(words, B: int, V: int, name: str) -> None:
+    if words.dtype != torch.int16:
+        raise TypeError(f"{name}: the history words are int16, got {words.dtype}")
+    if words.dim() != 2 or words.shape[0] < B or words.shape[1] < V or words.stride(1) != 1:
+        raise ValueError(f"{name}: words {tuple(words.shape)} (strides {words.stride()}) do not cover [{B}, {V}]")
+
+
+def _row_f32(t, B: int, name: str) -> None:
+    if t.dtype != torch.float32 or t.dim() != 1 or t.shape[0] < B or t.stride(0) != 1:
+        raise TypeError(f"{name}: expected a contiguous float32 [{B}] tensor, got {t.dtype} {tuple(t.shape)}")
+
+
+def penalty_seed(words_row, ids):
+    """Mark the context bit (bit 15) of ``ids`` (int32 [n]) in one row of penalty history words
+    (int16 [V]) that the caller zeroed first. Ids outside [0, V) are skipped."""
+    if words_row.dtype != torch.int16 or words_row.dim() != 1 or words_row.stride(0) != 1:
+        raise TypeError("penalty_seed: words_row is a contiguous int16 [V] row")
+    if ids.dtype != torch.int32 or ids.dim() != 1 or not ids.is_contiguous():
+        raise TypeError("penalty_seed: ids is a contiguous int32 [n] tensor")
+    V = words_row.shape[0]
+    if not words_row.is_cuda:
+        ok = ids[(ids >= 0) & (ids < V)].long()
+        words_row[ok] = -0x8000
+        return words_row
+    kernels().penalty_seed(_p(words_row), V, _p(ids), ids.numel(), _s(words_row))
+    return words_row
+
+
+def penalize_logits(logits, words, rep, freq, pres):
+    """The sampling penalties on float32 ``logits`` [B, V], in place, from the rows' history words
+    (``oracle.penalize_row`` states the arithmetic). ``ops.sample`` launches it itself when it is
+    given the words; this entry serves the tests of the kernel alone."""
+    B, V = logits.shape
+    _words_check(words, B, V, "penalize_logits")
+    if logits.dtype != torch.float32 or logits.stride(1) != 1:
+        raise TypeError("penalize_logits: float32 logits with unit column stride")
+    for t, name in ((rep, "rep"), (freq, "freq"), (pres, "pres")):
+        _row_f32(t, B, f"penalize_logits: {name}")
+    if not logits.is_cuda:
+        for b in range(B):
+            oracle.penalize_row(logits[b], words[b, :V], float(rep[b]), float(freq[b]), float(pres[b]))
+        return logits
+    kernels().penalize_logits(_p(logits), logits.stride(0), B, V, _p(words), words.stride(0), _p(rep), _p(freq),
+                              _p(pres), _s(logits))
+    return logits
+
+
 def sample(logits, inv_temp, top_k, top_p, seeds, positions, next_tok, workspace_v=None, workspace_i=None,
            tokens_in=None, seq_lens=None, slots=None, block_tables=None, bs=0, out_tokens=None, out_count=None,
-           use_topkp: bool = False):
-    """Sample one token per row and (optionally) advance the device decode state in the same launch."""
+           use_topkp: bool = False, *, words=None, rep=None, freq=None, pres=None, ln_min_p=None):
+    """Sample one token per row and (optionally) advance the device decode state in the same launch.
+
+    ``words`` ([B, >= V] int16 penalty history words) with ``rep`` / ``freq`` / ``pres`` ([B] float32):
+    the logits are penalised in place by a launch of their own first, and the state advance counts
+    the sampled id in the row's words. ``ln_min_p`` ([B] float32, log(min_p); -inf = off) is read by
+    the top-k/top-p launch only: the caller sets ``use_topkp`` when a row has min_p > 0."""
+    B, V = logits.shape
+    if words is not None:
+        _words_check(words, B, V, "sample")
+        if rep is None or freq is None or pres is None:
+            raise ValueError("sample: words come with rep, freq and pres")
+    if ln_min_p is not None:
+        _row_f32(ln_min_p, B, "sample: ln_min_p")
     if not logits.is_cuda:
-        tok = oracle.sample(logits, inv_temp, top_k, top_p, seeds, positions)
+        res = oracle.sample(logits, inv_temp, top_k, top_p, seeds, positions, words=words, rep=rep, freq=freq,
+                            pres=pres, ln_min_p=ln_min_p if use_topkp else None)
+        tok = res if words is None else res[0]
+        if words is not None and tokens_in is not None:
+            words.copy_(res[1])
         next_tok.copy_(tok)
         _advance_cpu(tok, tokens_in, positions, seq_lens, slots, block_tables, bs, out_tokens, out_count)
         return next_tok
-    B, V = logits.shape
+    if words is not None:
+        penalize_logits(logits, words, rep, freq, pres)
     cap = out_tokens.shape[1] if out_tokens is not None else 0
     kernels().sample(_p(logits), logits.stride(0), B, V, _p(inv_temp), _p(top_k), _p(top_p), _p(seeds), _p(positions),
                      _p(workspace_v), _p(workspace_i), _p(next_tok), _p(tokens_in), _p(seq_lens), _p(slots),
                      _p(block_tables), block_tables.stride(0) if block_tables is not None else 0, bs, _p(out_tokens),
-                     _p(out_count), cap, 1 if use_topkp else 0, _s(logits))
+                     _p(out_count), cap, 1 if use_topkp else 0, _p(words), words.stride(0) if words is not None else 0,
+                     _p(ln_min_p), _s(logits))
     return next_tok
 
 

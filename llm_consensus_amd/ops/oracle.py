@@ -195,13 +195,62 @@ def gumbel(key: int, idx: torch.Tensor, step: int) -> torch.Tensor:
     return -torch.log(-torch.log(u))
 
 
-def sample(logits: torch.Tensor, inv_temp, top_k, top_p, seeds, positions) -> torch.Tensor:
-    """Reference sampler: greedy if inv_temp <= 0; else Gumbel-max over the top-k/top-p set."""
+WORD_CTX, WORD_COUNT = 0x8000, 0x7FFF  # penalty history word: context bit, generated count (saturating)
+
+
+def fma32(a: torch.Tensor, b: torch.Tensor, c: torch.Tensor) -> torch.Tensor:
+    """float32 fused multiply-add a * b + c, rounded once (the device's v_fma_f32): the product of
+    two float32 is exact in float64, the sum is rounded to odd there (TwoSum tells whether it was
+    exact), and rounding that to float32 cannot round twice."""
+    prod = a.double() * b.double()
+    cd = c.double()
+    s = prod + cd
+    bb = s - prod
+    err = (prod - (s - bb)) + (cd - bb)
+    fix = torch.isfinite(s) & (err != 0) & ((s.view(torch.int64) & 1) == 0)
+    toward = torch.where(err > 0, torch.full_like(s, float("inf")), torch.full_like(s, float("-inf")))
+    return torch.where(fix, torch.nextafter(s, toward), s).float()
+
+
+def penalize_row(row: torch.Tensor, words: torch.Tensor, rep: float, freq: float, pres: float) -> None:
+    """The sampling penalties of csrc/kernels/sampler.hip (penalize_logits_kernel) on one float32
+    row, in place and to the bit: where the id's history word is non-zero l = l > 0 ? l / r : l * r;
+    where its generated count c > 0, l = fma(-f, c, l) - p. A neutral row is left alone."""
+    f32 = lambda v: torch.tensor(v, dtype=torch.float32)  # noqa: E731
+    r, f, p = f32(rep), f32(freq), f32(pres)
+    if float(r) == 1.0 and float(f) == 0.0 and float(p) == 0.0:
+        return
+    w = words.to(torch.int32) & 0xFFFF
+    seen = torch.nonzero(w != 0).flatten()
+    if seen.numel() == 0:
+        return
+    l = row[seen]
+    l = torch.where(l > 0, l / r, l * r)
+    c = w[seen] & WORD_COUNT
+    gen = c > 0
+    if bool(gen.any()):
+        l[gen] = fma32((-f).expand(int(gen.sum())), c[gen].float(), l[gen]) - p
+    row[seen] = l
+
+
+def sample(logits: torch.Tensor, inv_temp, top_k, top_p, seeds, positions, *, words=None, rep=None, freq=None,
+           pres=None, ln_min_p=None):
+    """Reference sampler: greedy if inv_temp <= 0; else Gumbel-max over the top-k/top-p set.
+
+    ``words`` ([B, >= V] int16 history words) with ``rep`` / ``freq`` / ``pres`` ([B] float32): the
+    rows are penalised first (``penalize_row``), written back into ``logits``, and the call returns
+    (tokens, words with the sampled ids counted) instead of the tokens alone. ``ln_min_p`` ([B]
+    float32, log(min_p); -inf = off): sampled rows keep l, after top-k / top-p, iff it is the row
+    maximum or (l - max) * inv_temp >= ln_min_p in float32."""
     B, V = logits.shape
     out = torch.empty(B, dtype=torch.int32)
     idx = torch.arange(V)
     for b in range(B):
         row = logits[b].float()
+        if words is not None and rep is not None:
+            row = row.clone()
+            penalize_row(row, words[b, :V], float(rep[b]), float(freq[b]), float(pres[b]))
+            logits[b].copy_(row)
         it = float(inv_temp[b])
         k = int(top_k[b]) if top_k is not None else 0
         p = float(top_p[b]) if top_p is not None else 1.0
@@ -219,6 +268,11 @@ def sample(logits: torch.Tensor, inv_temp, top_k, top_p, seeds, positions) -> to
             cut = min(cut, V - 1)
             thr = row[order[cut]]
             keep &= row >= thr
+        lmp = float(ln_min_p[b]) if ln_min_p is not None else float("-inf")
+        if it > 0 and lmp > float("-inf"):
+            m = torch.where(torch.isnan(row), torch.tensor(float("-inf")), row).max()
+            f32 = torch.float32
+            keep &= (row == m) | ((row - m) * torch.tensor(it, dtype=f32) >= torch.tensor(lmp, dtype=f32))
         if it <= 0:
             v = torch.where(keep, row, torch.tensor(float("-inf")))
         else:
@@ -227,7 +281,15 @@ def sample(logits: torch.Tensor, inv_temp, top_k, top_p, seeds, positions) -> to
         mx = v.max()
         hit = torch.nonzero(v == mx)
         out[b] = int(hit[0].item()) if hit.numel() else 0  # all-NaN row: id 0, as the kernels write
-    return out
+    if words is None:
+        return out
+    counted = words.clone()
+    for b in range(B):
+        w = int(counted[b, int(out[b])]) & 0xFFFF
+        if w & WORD_COUNT != WORD_COUNT:
+            w += 1
+            counted[b, int(out[b])] = w - 0x10000 if w >= 0x8000 else w
+    return out, counted
 
 
 # -- MoE ------------------------------------------------------------------------------------------

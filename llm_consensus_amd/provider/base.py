@@ -13,6 +13,7 @@ nanosecond value is kept in ``latency_ns`` for benches.
 from __future__ import annotations
 
 import dataclasses
+import math
 from typing import Callable, Optional, Protocol
 
 from ..context import Context
@@ -32,6 +33,31 @@ class Request:
     top_k: Optional[int] = None
     seed: Optional[int] = None
     stop_on_eos: Optional[bool] = None  # None = stop at the model's EOS (benchmarks pin full lengths)
+    # sampling penalties and min-p (local engines; the stub and the hosted providers ignore them)
+    min_p: Optional[float] = None
+    repetition_penalty: Optional[float] = None
+    presence_penalty: Optional[float] = None
+    frequency_penalty: Optional[float] = None
+
+
+def check_sampling(min_p=None, repetition_penalty=None, presence_penalty=None, frequency_penalty=None) -> None:
+    """Raise ValueError("<name>: <why>") for a value no engine may see (``None`` = not given)."""
+    def num(name, v):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
+            raise ValueError(f"{name}: expected a finite number, got {v!r}")
+
+    if min_p is not None:
+        num("min_p", min_p)
+        if not 0.0 <= min_p <= 1.0:
+            raise ValueError(f"min_p: expected a value in [0, 1], got {min_p!r}")
+    if repetition_penalty is not None:
+        num("repetition_penalty", repetition_penalty)
+        if not repetition_penalty > 0.0:
+            raise ValueError(f"repetition_penalty: expected a value above 0, got {repetition_penalty!r}")
+    if presence_penalty is not None:
+        num("presence_penalty", presence_penalty)
+    if frequency_penalty is not None:
+        num("frequency_penalty", frequency_penalty)
 
 
 @dataclasses.dataclass

@@ -82,6 +82,33 @@ class LocalError(Exception):
     pass
 
 
+# (request field, neutral value, type): the sampling knobs a request carries to the engine
+_KNOBS = (("temperature", 1.0, float), ("top_p", 1.0, float), ("top_k", 0, int), ("min_p", 0.0, float),
+          ("repetition_penalty", 1.0, float), ("presence_penalty", 0.0, float), ("frequency_penalty", 0.0, float))
+
+
+def sampling_knobs(req: Optional[Request], config, model_sampling: bool) -> dict:
+    """SamplingParams fields of a request. With ``model_sampling`` a checkpoint model's own values
+    (``ModelConfig.sampling``) stand in for every knob the request left neutral (not given, or
+    temperature 1, top_k 0, top_p 1, min_p 0, repetition_penalty 1)."""
+    own = getattr(config, "sampling", None) if model_sampling else None
+    out = {}
+    for name, neutral, typ in _KNOBS:
+        v = getattr(req, name, None) if req is not None else None
+        v = neutral if v is None else typ(v)
+        if v == neutral and own is not None and hasattr(own, name):
+            v = typ(getattr(own, name))
+        out[name] = v
+    return out
+
+
+def sampling_form(req: Optional[Request], config, model_sampling: bool) -> tuple:
+    """(top-k/top-p launch, penalty launch) the decode graphs of such requests carry."""
+    k = sampling_knobs(req, config, model_sampling)
+    return (k["top_k"] > 0 or k["top_p"] < 1.0 or k["min_p"] > 0.0,
+            k["repetition_penalty"] != 1.0 or k["presence_penalty"] != 0.0 or k["frequency_penalty"] != 0.0)
+
+
 def _free_port() -> int:
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -146,13 +173,18 @@ class LocalBackend:
     def __init__(self, specs: List[ModelSpec], judge: Optional[str] = None, gpus: Optional[List[int]] = None,
                  trace: bool = False, counts: Optional[Dict[str, int]] = None,
                  max_context: Optional[Dict[str, int]] = None, start_timeout: float = 1800.0,
-                 pins: Optional[Dict[str, List[int]]] = None, judge_tp: int = 0, concurrency: int = 1):
+                 pins: Optional[Dict[str, List[int]]] = None, judge_tp: int = 0, concurrency: int = 1,
+                 sampling: Optional[Request] = None, model_sampling: bool = False):
         """``concurrency``: consensus requests served at once (the server): each engine gets decode
         rows for that many requests (replica batching, up to 4 rows) and KV for their sequences
-        plus one judge session per request."""
+        plus one judge session per request. ``sampling``: the run's request template; the workers
+        also capture the decode graphs of its sampling form (top-k/top-p launch, penalties) when it
+        is not the default one. ``model_sampling``: a checkpoint model samples with its
+        generation_config.json values for every knob a request leaves neutral."""
         import multiprocessing as mp
 
         self.specs = {s.name: s for s in specs}
+        self.model_sampling = bool(model_sampling)
         self.judge = judge
         force_cpu = os.environ.get("LLMC_DEVICE", "") == "cpu"
         # CPU workers (tests): LLMC_CPU_WORKERS=k spreads the models over k worker processes
@@ -235,7 +267,9 @@ class LocalBackend:
                                    "fused_ar": fused[m],
                                    # no other engine decodes on its GPUs meanwhile: the lone-engine
                                    # launch forms (ops.attn_oproj_min_chunk)
-                                   "alone": alone[m]})
+                                   "alone": alone[m],
+                                   # (top-k/top-p launch, penalty launch) of the run's requests
+                                   "sampling_form": sampling_form(sampling, s.config, self.model_sampling)})
             if groups:
                 dist_info = {"port": port, "rank": rank_of[g], "world": len(used),
                              "groups": [(m, [rank_of[x] for x in gs]) for m, gs in groups]}
@@ -347,9 +381,10 @@ class LocalProvider:
             raise LocalError(f"prompt of {prompt_len} tokens exceeds {self.model} context {self.backend._ctx[self.model]}")
         mt = min(req.max_tokens or DEFAULT_MAX_TOKENS, ctx_cap)
         seed = req.seed if req.seed is not None else (zlib.crc32(self.model.encode()) & 0x7FFFFFFF)
-        return {"max_tokens": int(mt), "temperature": 1.0 if req.temperature is None else float(req.temperature),
-                "top_p": 1.0 if req.top_p is None else float(req.top_p), "top_k": int(req.top_k or 0),
-                "seed": int(seed), "stop_on_eos": True if req.stop_on_eos is None else bool(req.stop_on_eos)}
+        out = sampling_knobs(req, self.spec.config, self.backend.model_sampling)
+        out.update({"max_tokens": int(mt), "seed": int(seed),
+                    "stop_on_eos": True if req.stop_on_eos is None else bool(req.stop_on_eos)})
+        return out
 
     def _stream(self, ctx: Context, rid: int, q: "queue.Queue", callback: Optional[StreamCallback], t0: int,
                 prompt_tokens: int) -> Response:

@@ -430,6 +430,7 @@ def worker_main(gpu: int, conn, models: List[dict], dist_info: Optional[dict], t
         hosts: Dict[str, _EngineHost] = {}
         ctxs: Dict[int, Context] = {}  # live requests' contexts (cancel); dropped when they finish
         faults = parse_faults(os.environ.get("LLMC_FAULT", ""))
+        forms = {m["name"]: tuple(m.get("sampling_form") or (False, False)) for m in models}
         for m in models:
             cfg = FAMILIES.get(m["family"])
             if cfg is None and m.get("checkpoint"):  # --weights-dir family (spawned: re-register)
@@ -468,6 +469,11 @@ def worker_main(gpu: int, conn, models: List[dict], dist_info: Optional[dict], t
             for h in hosts.values():
                 with trace.span("graph_warmup", engine=h.name):
                     h.engine.warmup_graphs()
+                    # ... and those of the run's sampling form when it is not the default one, so a
+                    # top-k or penalised run does not decode eagerly in a process of several engines
+                    topkp, pen = forms.get(h.name, (False, False))
+                    if topkp or pen:
+                        h.engine.warmup_graphs(topkp=topkp, penalties=pen)
             torch.cuda.synchronize()
         send(("ready", {"gpu": gpu, "models": list(hosts)}))
     except Exception as e:  # noqa: BLE001

@@ -11,6 +11,8 @@ order (``internal/runner``), single-response passthrough and judge template
   GET  /v1/models          served models and their providers
   POST /v1/consensus       {"prompt": "...", "models": [...], "judge": "...", "max_tokens": N,
                             "temperature": T, "top_p": P, "top_k": K, "seed": S, "timeout": SEC,
+                            "min_p": M, "repetition_penalty": R, "presence_penalty": PP,
+                            "frequency_penalty": FP,
                             "stream": false}
        stream=false: 200 + the Go-compatible result JSON (byte-identical to result.json)
        stream=true:  200 text/event-stream: model_start / chunk / tokens / model_done /
@@ -40,7 +42,7 @@ from typing import Callable, List, Optional
 from .consensus import Judge, prompt_header, response_block
 from .context import Context
 from .output import Result, encode_result
-from .provider.base import Request, Response
+from .provider.base import Request, Response, check_sampling
 from .runner import Callbacks, Runner
 
 EventFn = Callable[[str, dict], None]
@@ -85,18 +87,25 @@ class ConsensusService:
 
     def __init__(self, models: List[str], judge: str, gpus: str = "", placement: str = "", judge_tp: int = 0,
                  concurrency: int = 4, timeout: float = 120.0, max_tokens: int = 0, temperature: float = 1.0,
-                 top_p: float = 1.0, top_k: int = 0, seed: int = 0):
+                 top_p: float = 1.0, top_k: int = 0, seed: int = 0, min_p: float = 0.0,
+                 repetition_penalty: float = 1.0, presence_penalty: float = 0.0, frequency_penalty: float = 0.0,
+                 model_sampling: bool = False):
         from .cli import Config, init_registry
+
+        pen = dict(min_p=min_p, repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
+                   frequency_penalty=frequency_penalty)
+        check_sampling(**pen)  # before any engine starts
 
         self.responders = list(dict.fromkeys(models))
         self.judge = judge
         self.timeout = timeout
         self.concurrency = max(1, concurrency)
-        self.defaults = dict(max_tokens=max_tokens, temperature=temperature, top_p=top_p, top_k=top_k, seed=seed)
+        self.defaults = dict(max_tokens=max_tokens, temperature=temperature, top_p=top_p, top_k=top_k, seed=seed,
+                             **pen)
         cfg = Config(models=self.responders, judge=judge, file="", output="", data_dir="", timeout=timeout,
                      prompt="", quiet=True, json=True, no_save=True, max_tokens=max_tokens,
                      temperature=temperature, top_p=top_p, top_k=top_k, seed=seed, gpus=gpus, trace=False,
-                     placement=placement, judge_tp=judge_tp)
+                     placement=placement, judge_tp=judge_tp, model_sampling=model_sampling, **pen)
         self.registry = init_registry(cfg, concurrency=self.concurrency)
         self.served = self.registry.models()
         self._slots = threading.BoundedSemaphore(self.concurrency)
@@ -137,7 +146,14 @@ class ConsensusService:
                 raise BadRequest(f"initializing provider for {m}: unknown model {json.dumps(m)}; "
                                  f"available models: [{' '.join(self.served)}]")
         d = self.defaults
+        pen = {k: self._param(body, k, float, d[k])
+               for k in ("min_p", "repetition_penalty", "presence_penalty", "frequency_penalty")}
+        try:
+            check_sampling(**pen)
+        except ValueError as e:
+            raise BadRequest(str(e)) from None
         return {
+            **pen,
             "prompt": prompt, "models": models, "judge": judge,
             "timeout": self._param(body, "timeout", float, self.timeout),
             "max_tokens": self._param(body, "max_tokens", int, d["max_tokens"]),
@@ -172,7 +188,9 @@ class ConsensusService:
         prompt, models, judge_name = req["prompt"], req["models"], req["judge"]
         tmpl = Request(model="", prompt="", max_tokens=req["max_tokens"] or None, temperature=req["temperature"],
                        top_p=req["top_p"], top_k=req["top_k"] or None, seed=req["seed"] or None,
-                       stop_on_eos=req.get("stop_on_eos"))
+                       stop_on_eos=req.get("stop_on_eos"), min_p=req.get("min_p"),
+                       repetition_penalty=req.get("repetition_penalty"), presence_penalty=req.get("presence_penalty"),
+                       frequency_penalty=req.get("frequency_penalty"))
         jp = self.registry.get(judge_name)
         session = None
         if hasattr(jp, "new_session") and len(models) > 1 and judge_name == self.judge:
@@ -338,16 +356,29 @@ def main(argv: Optional[List[str]] = None) -> int:
     ap.add_argument("--top-p", type=float, default=1.0)
     ap.add_argument("--top-k", type=int, default=0)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--min-p", type=float, default=0.0)
+    ap.add_argument("--repetition-penalty", type=float, default=1.0)
+    ap.add_argument("--presence-penalty", type=float, default=0.0)
+    ap.add_argument("--frequency-penalty", type=float, default=0.0)
+    ap.add_argument("--model-sampling", action="store_true",
+                    help="checkpoint models sample with their generation_config.json values where a knob is neutral")
     ap.add_argument("--gpus", default="")
     ap.add_argument("--placement", default="")
     ap.add_argument("--judge-tp", type=int, default=0)
     ap.add_argument("--verbose", action="store_true")
     a = ap.parse_args(argv)
     t0 = time.monotonic()
+    try:
+        check_sampling(min_p=a.min_p, repetition_penalty=a.repetition_penalty, presence_penalty=a.presence_penalty,
+                       frequency_penalty=a.frequency_penalty)
+    except ValueError as e:
+        ap.error(str(e))
     svc = ConsensusService([m.strip() for m in a.models.split(",") if m.strip()], a.judge, gpus=a.gpus,
                            placement=a.placement, judge_tp=a.judge_tp, concurrency=a.concurrency,
                            timeout=a.timeout, max_tokens=a.max_tokens, temperature=a.temperature, top_p=a.top_p,
-                           top_k=a.top_k, seed=a.seed)
+                           top_k=a.top_k, seed=a.seed, min_p=a.min_p, repetition_penalty=a.repetition_penalty,
+                           presence_penalty=a.presence_penalty, frequency_penalty=a.frequency_penalty,
+                           model_sampling=a.model_sampling)
 
     def ready(port: int) -> None:
         sys.stderr.write(f"llm-consensus server: {len(svc.served)} models ready in {time.monotonic() - t0:.1f}s, "
