@@ -77,6 +77,9 @@ int llmc_sample_parts();
 int llmc_penalize_logits(void*, int64_t, int, int, const void*, int64_t, const void*, const void*, const void*,
                          hipStream_t);
 int llmc_penalty_seed(void*, int, const void*, int, hipStream_t);
+int llmc_logprobs_stage1(const void*, int64_t, int, int, int, void*, void*, void*, void*, hipStream_t);
+int llmc_logprobs_stage2(const void*, int64_t, int, int, int, const void*, const void*, const void*, const void*,
+                         const void*, const void*, int, void*, void*, void*, int, hipStream_t);
 int llmc_moe_route(const void*, int, int, int, void*, void*, hipStream_t);
 int llmc_moe_down_combine(int, const void*, int, const void*, const void*, const void*, void*, int, int, int, int,
                           hipStream_t);
@@ -326,6 +329,15 @@ PYBIND11_MODULE(_llmc_hip, m) {
     check(llmc_penalty_seed(P(words_row), V, P(ids), n, S(s)), "penalty_seed");
   });
   m.def("sample_parts", []() { return llmc_sample_parts(); });
+  m.def("logprobs_stage1", [](ptr logits, int64_t rs, int B, int V, int N, ptr pm, ptr ps, ptr cv, ptr ci, ptr s) {
+    check(llmc_logprobs_stage1(P(logits), rs, B, V, N, P(pm), P(ps), P(cv), P(ci), S(s)), "logprobs_stage1");
+  });
+  m.def("logprobs_stage2", [](ptr raw, int64_t rs, int B, int V, int N, ptr tokens, ptr pm, ptr ps, ptr cv, ptr ci,
+                              ptr oc, int cap, ptr lt, ptr tv, ptr ti, int tstride, ptr s) {
+    check(llmc_logprobs_stage2(P(raw), rs, B, V, N, P(tokens), P(pm), P(ps), P(cv), P(ci), P(oc), cap, P(lt), P(tv),
+                               P(ti), tstride, S(s)),
+          "logprobs_stage2");
+  });
   m.def("moe_route", [](ptr logits, int T, int E, int k, ptr w, ptr ids, ptr s) {
     check(llmc_moe_route(P(logits), T, E, k, P(w), P(ids), S(s)), "moe_route");
   });

@@ -28,7 +28,7 @@ from .catalog import PROVIDER_LOCAL, PROVIDER_STUB, UnknownModel, dump_catalog, 
 from .consensus import Judge, prompt_header, response_block
 from .context import Context
 from .flags import FlagSet, parse_or_exit
-from .output import Result, encode_result
+from .output import Result, encode_result, logprob_summary, logprobs_object
 from .provider.base import Request, check_sampling
 from .provider.registry import Registry
 from .runner import Callbacks, Runner
@@ -71,6 +71,7 @@ class Config:
     presence_penalty: float = 0.0
     frequency_penalty: float = 0.0
     model_sampling: bool = False
+    logprobs: Optional[int] = None  # None = off
 
 
 def make_flagset() -> FlagSet:
@@ -96,6 +97,8 @@ def make_flagset() -> FlagSet:
     fs.add("repetition-penalty", "float", 1.0, "Divide / multiply the logits of ids in the context or generated (1 = off)")
     fs.add("presence-penalty", "float", 0.0, "Subtracted from the logits of generated ids")
     fs.add("frequency-penalty", "float", 0.0, "Subtracted from the logits of generated ids, times their count")
+    fs.add("logprobs", "int", -1,
+           "Save every token's raw log-probability and the N most likely alternatives (0-20) to logprobs.json (-1 = off)")
     fs.add("model-sampling", "bool", False,
            "Checkpoint models sample with their generation_config.json values where a flag is left neutral")
     fs.add("gpus", "string", "", "Comma-separated GPU ids to place models on (default: all visible)")
@@ -179,6 +182,13 @@ def parse_flags(argv: List[str], stdout: TextIO = sys.stdout, stderr: TextIO = s
             stderr.write(f'invalid value "{_go_num(v[name])}" for flag -{flag}: {str(e).split(": ", 1)[1]}\n{fs.usage()}')
             stderr.flush()
             raise SystemExit(2)
+    if v["logprobs"] != -1:
+        try:
+            check_sampling(logprobs=v["logprobs"])
+        except ValueError as e:
+            stderr.write(f'invalid value "{v["logprobs"]}" for flag -logprobs: {str(e).split(": ", 1)[1]}\n{fs.usage()}')
+            stderr.flush()
+            raise SystemExit(2)
     wd = v["weights_dir"] or os.environ.get("LLMC_WEIGHTS_DIR", "")
     if wd:
         register_weights(wd)
@@ -199,7 +209,8 @@ def parse_flags(argv: List[str], stdout: TextIO = sys.stdout, stderr: TextIO = s
                  judge_tp=v["judge_tp"], server=v["server"] or os.environ.get("LLMC_SERVER", ""),
                  judge_explicit=any(a.lstrip("-").split("=")[0] == "judge" for a in argv[:len(argv) - len(rest)]),
                  min_p=v["min_p"], repetition_penalty=v["repetition_penalty"], presence_penalty=v["presence_penalty"],
-                 frequency_penalty=v["frequency_penalty"], model_sampling=v["model_sampling"])
+                 frequency_penalty=v["frequency_penalty"], model_sampling=v["model_sampling"],
+                 logprobs=None if v["logprobs"] == -1 else v["logprobs"])
     cfg.prompt = get_prompt(rest, cfg.file, stdin)
     return cfg
 
@@ -282,7 +293,7 @@ def _request_template(cfg: Config) -> Request:
     return Request(model="", prompt="", max_tokens=cfg.max_tokens or None, temperature=cfg.temperature,
                    top_p=cfg.top_p, top_k=cfg.top_k or None, seed=cfg.seed or None, min_p=cfg.min_p,
                    repetition_penalty=cfg.repetition_penalty, presence_penalty=cfg.presence_penalty,
-                   frequency_penalty=cfg.frequency_penalty)
+                   frequency_penalty=cfg.frequency_penalty, logprobs=cfg.logprobs)
 
 
 def _go_num(v) -> str:
@@ -360,6 +371,8 @@ def _run_with_registry(cfg: Config, registry: Registry, ctx: Context, show_ui: b
 
     out = Result(prompt=cfg.prompt, responses=result.responses, consensus=consensus, judge=cfg.judge,
                  warnings=result.warnings, failed_models=result.failed_models)
+    if cfg.logprobs is not None:
+        out.logprobs = logprobs_object(result.responses, judge.last_response)
     _write_outputs(cfg, out, show_ui, start, stdout, stderr, registry)
 
 
@@ -384,6 +397,17 @@ def _write_outputs(cfg: Config, out: Result, show_ui: bool, start: float, stdout
             except OSError as e:
                 if show_ui:
                     ui.print_error(stderr, f"Failed to save {label}: {_go_path_err('open', os.path.join(run_dir, fname), e)}")
+        if out.logprobs is not None:  # beside result.json, which stays byte for byte what it is without the flag
+            import json
+
+            lp = dict(out.logprobs)
+            lp["summary"] = {"responses": {m: logprob_summary(e) for m, e in lp["responses"].items()},
+                             "judge": logprob_summary(lp["judge"])}
+            try:
+                _write_file(os.path.join(run_dir, "logprobs.json"), (json.dumps(lp, indent=2) + "\n").encode())
+            except OSError as e:
+                if show_ui:
+                    ui.print_error(stderr, f"Failed to save logprobs: {_go_path_err('open', os.path.join(run_dir, 'logprobs.json'), e)}")
         if cfg.trace and registry is not None:
             from .utils import trace
 
@@ -438,6 +462,9 @@ def _run_remote(cfg: Config, ctx: Context, show_ui: bool, stderr: TextIO) -> Res
             "top_k": cfg.top_k or None, "seed": cfg.seed or None, "min_p": cfg.min_p,
             "repetition_penalty": cfg.repetition_penalty, "presence_penalty": cfg.presence_penalty,
             "frequency_penalty": cfg.frequency_penalty}
+    if cfg.logprobs is not None:
+        body["logprobs"] = cfg.logprobs
+    lp_resp, lp_judge = {}, []
     if cfg.judge_explicit:
         body["judge"] = cfg.judge
     conn_cls = http.client.HTTPSConnection if u.scheme == "https" else http.client.HTTPConnection
@@ -497,6 +524,10 @@ def _run_remote(cfg: Config, ctx: Context, show_ui: bool, stderr: TextIO) -> Res
                 progress.model_tokens(d["model"], d["n"])
             elif ev == "model_done":
                 progress.model_completed(d["model"])
+                if "logprobs" in d:
+                    lp_resp[d["model"]] = d["logprobs"]
+            elif ev == "judge_done":
+                lp_judge = d.get("logprobs", [])
             elif ev == "model_error":
                 progress.model_failed(d["model"], Exception(d["error"]))
             elif ev == "judge_start":
@@ -533,7 +564,9 @@ def _run_remote(cfg: Config, ctx: Context, show_ui: bool, stderr: TextIO) -> Res
                   responses=[Response(model=x["model"], content=x["content"], provider=x["provider"],
                                       latency_ns=int(x["latency_ms"]) * 1_000_000) for x in r["responses"] or []],
                   consensus=r["consensus"], judge=r["judge"], warnings=r.get("warnings"),
-                  failed_models=r.get("failed_models"))
+                  failed_models=r.get("failed_models"),
+                  logprobs=({"responses": {x["model"]: lp_resp.get(x["model"], []) for x in r["responses"] or []},
+                             "judge": lp_judge} if cfg.logprobs is not None else None))
 
 
 def _write_file(path: str, data: bytes) -> None:

@@ -84,6 +84,7 @@ class Judge:
         self.provider = provider
         self.model = model
         self._tmpl = request_template
+        self.last_response: Optional[Response] = None  # of the last synthesis that queried the judge
 
     def synthesize(self, ctx: Context, original_prompt: str, responses: List[Response]) -> str:
         return self.synthesize_stream(ctx, original_prompt, responses, None)
@@ -113,4 +114,5 @@ class Judge:
                 resp = self.provider.query_stream(ctx, req, callback)
         except Exception as e:  # noqa: BLE001
             raise JudgeError(f"judge query failed: {e}") from e
+        self.last_response = resp
         return resp.content

@@ -29,7 +29,7 @@ TokenFn = Callable[["Row", List[int]], None]
 
 
 class Row:
-    __slots__ = ("seq", "params", "tag", "produced", "issued", "base", "done", "error", "ctx", "tokens")
+    __slots__ = ("seq", "params", "tag", "produced", "issued", "base", "done", "error", "ctx", "tokens", "logprobs")
 
     def __init__(self, seq: Sequence, params: SamplingParams, tag, ctx):
         self.seq = seq
@@ -42,14 +42,17 @@ class Row:
         self.done = False
         self.error: Optional[BaseException] = None
         self.tokens: List[int] = []
+        # one (logprob, [(id, logprob), ...]) entry per token when params.logprobs asks, else None
+        self.logprobs: Optional[list] = [] if params.logprobs is not None else None
 
 
 class ContinuousBatcher:
-    def __init__(self, engine: Engine, on_tokens: Optional[TokenFn] = None):
+    def __init__(self, engine: Engine, on_tokens: Optional[TokenFn] = None, on_logprobs=None):
         if engine.tp.size != 1:
             raise EngineError("continuous batching needs a TP=1 engine")
         self.e = engine
         self.on_tokens = on_tokens
+        self.on_logprobs = on_logprobs  # on_logprobs(row, entries), right after on_tokens(row, new)
         self.rows: List[Row] = []
         self._pending = None          # event of the in-flight host snapshot
         self._snap: List[Row] = []    # row layout the snapshot was taken with
@@ -86,6 +89,7 @@ class ContinuousBatcher:
             e.positions[r] = seq.length - 1
             e.out_count[r] = 0
             e._use_topkp, e._use_penalties = params.topkp, params.penalised
+            e._use_logprobs = params.logprobs is not None
             e._sample(1, e.logits_local[r:r + 1], r0=r)
         seq.row = r
         row = Row(seq, params, tag, ctx)
@@ -118,6 +122,16 @@ class ContinuousBatcher:
                     except Exception as ex:  # noqa: BLE001 - the row's consumer failed: retire it
                         row.error, row.done = ex, True
                         continue
+                if row.logprobs is not None:
+                    ent = self.e._logprob_entries(toks is not self.e.out_tokens, i, row.produced,
+                                                  row.produced + len(new), p.logprobs)
+                    row.logprobs.extend(ent)
+                    if self.on_logprobs is not None:
+                        try:
+                            self.on_logprobs(row, ent)
+                        except Exception as ex:  # noqa: BLE001
+                            row.error, row.done = ex, True
+                            continue
             row.produced = n if not stop else row.produced + len(new)
             if stop or n >= p.max_tokens:
                 row.done = True
@@ -139,6 +153,10 @@ class ContinuousBatcher:
                 if s != t:
                     for buf in self._row_state + self._penalty_state():
                         buf[t].copy_(buf[s])
+                    if row.logprobs is not None:  # the columns not yet consumed travel with the row
+                        for buf in (self.e.lp_tok, self.e.lp_top_v, self.e.lp_top_i):
+                            hi = min(self.e.cap, row.issued)
+                            buf[t, row.produced:hi].copy_(buf[s, row.produced:hi])
                     row.seq.row = t
         self.rows = keep
         for row in gone:
@@ -161,6 +179,7 @@ class ContinuousBatcher:
                 bucket = e._bucket(max(r.base + r.issued for r in self.rows) + S + 1)
                 e._use_topkp = any(r.params.topkp for r in self.rows)
                 e._use_penalties = any(r.params.penalised for r in self.rows)
+                e._use_logprobs = any(r.params.logprobs is not None for r in self.rows)
                 graph = e._graph(B, bucket) if (e.on_gpu and e.ecfg.use_graphs) else None
                 if graph is not None:
                     graph.replay()
@@ -189,6 +208,9 @@ class ContinuousBatcher:
             # snapshot of the state after this replay (and the compaction), read next call
             e.host_count.copy_(e.out_count, non_blocking=True)
             e.host_tokens.copy_(e.out_tokens, non_blocking=True)
+            for i, r in enumerate(self.rows):
+                if r.logprobs is not None:
+                    e._copy_logprobs(i, r.produced, min(e.cap, r.issued))
             self._host_fault.copy_(e.attn_fault, non_blocking=True)
             # re-arm before the next replay is queued: a fault that replay raises lands in the next
             # snapshot instead of being wiped by a clear queued behind it

@@ -215,6 +215,9 @@ class SamplingParams:
     # over the ids generated so far: l -= presence_penalty + frequency_penalty x (times generated)
     presence_penalty: float = 0.0
     frequency_penalty: float = 0.0
+    # None = off; n in [0, 20]: report the raw log-probability of every generated token and of the n
+    # most likely ids at its step (before penalties, temperature and truncation)
+    logprobs: Optional[int] = None
 
     @property
     def penalised(self) -> bool:
@@ -228,6 +231,17 @@ class SamplingParams:
     @property
     def ln_min_p(self) -> float:
         return math.log(self.min_p) if self.min_p > 0.0 else float("-inf")
+
+
+LOGPROBS_WIDTH = 20  # places of the device top lists: the form is launch-uniform, rows truncate on the host
+
+
+class Tokens(list):
+    """What ``decode`` / ``generate_batch`` (a list of rows) and ``generate_ids`` (one row) return: the
+    token ids as before, plus ``logprobs``: per row ``None`` unless its ``SamplingParams.logprobs``
+    asked, else one ``(logprob, [(id, logprob), ...])`` entry per token."""
+
+    logprobs = None
 
 
 class Sequence:
@@ -395,6 +409,10 @@ class Engine:
         # penalised bind (_penalty_state); an engine that never sees a penalty never holds them
         self.pen_words: Optional[torch.Tensor] = None
         self.pen_rep = self.pen_freq = self.pen_pres = None
+        # token log-probabilities: the rings, the part workspaces and the host twins, allocated by the
+        # first bind that asks (_logprob_state)
+        self.lp_tok = self.lp_top_v = self.lp_top_i = self.lp_ws = self.lp_raw = None
+        self.host_lp_tok = self.host_lp_top_v = self.host_lp_top_i = None
         bf = dict(dtype=torch.bfloat16, device=dev)
         self.h = torch.zeros(B, c.hidden, **bf)
         self.q = torch.zeros(B, self.w.q_size, **bf)
@@ -869,7 +887,7 @@ class Engine:
             with self._on_stream():
                 self.prefill([seq], [list(prompt)])
                 self._reserve(seq, seq.length + 4)
-                self._use_topkp = self._use_penalties = False
+                self._use_topkp = self._use_penalties = self._use_logprobs = False
                 self._bind_rows([seq], [SamplingParams(2, 0.0, 1.0, 0, 0, False)])
                 self._sample(1, self._gather_logits(1))  # the prefill's token -> this step's input
                 pos = int(self.positions[0].item())
@@ -978,14 +996,59 @@ class Engine:
         pen = {}
         if self._use_penalties:
             pen = dict(words=self.pen_words[sl], rep=self.pen_rep[sl], freq=self.pen_freq[sl], pres=self.pen_pres[sl])
+        raw = logits
+        if self._use_logprobs:
+            # stage 1 reads the raw row, so it runs ahead of the penalty launch; stage 2 runs after the
+            # sampler and needs the raw row again for the sampled id: a copy when penalties rewrite it
+            ops.logprobs_stage1(logits, LOGPROBS_WIDTH, self.lp_ws)
+            if self._use_penalties:
+                if self.lp_raw is None:  # an eager step always comes first (decode's first token, a warm-up)
+                    self.lp_raw = torch.zeros(self.ecfg.max_batch, self.cfg.vocab, dtype=torch.float32,
+                                              device=self.device)
+                raw = self.lp_raw[:B]
+                raw.copy_(logits)
         ops.sample(logits, self.inv_temp[sl], self.top_k[sl], self.top_p[sl], self.seeds[sl], self.positions[sl],
                    self.next_tok[sl], self.ws_v[sl] if self.ws_v is not None else None,
                    self.ws_i[sl] if self.ws_i is not None else None, tokens_in=self.tokens_in[sl],
                    seq_lens=self.seq_lens[sl], slots=self.slots[sl], block_tables=self.block_tables[sl], bs=self.bs,
                    out_tokens=self.out_tokens[sl], out_count=self.out_count[sl], use_topkp=use_topkp,
                    ln_min_p=self.ln_min_p[sl], **pen)
+        if self._use_logprobs:
+            ops.logprobs_stage2(raw, self.next_tok[sl], LOGPROBS_WIDTH, self.lp_ws, self.lp_tok[sl], self.lp_top_v[sl],
+                                self.lp_top_i[sl], out_count=self.out_count[sl])
 
     _use_penalties = False
+    _use_logprobs = False
+
+    def _logprob_state(self) -> None:
+        """Allocate the log-probability rings [max_batch, cap(, 20)], the part workspaces and the pinned
+        host twins (first bind that asks)."""
+        if self.lp_tok is not None:
+            return
+        B, dev, W = self.ecfg.max_batch, self.device, LOGPROBS_WIDTH
+        self.lp_tok = torch.zeros(B, self.cap, dtype=torch.float32, device=dev)
+        self.lp_top_v = torch.zeros(B, self.cap, W, dtype=torch.float32, device=dev)
+        self.lp_top_i = torch.zeros(B, self.cap, W, dtype=torch.int32, device=dev)
+        self.lp_ws = ops.logprobs_workspace(B, W, dev)
+        if self.on_gpu:
+            self.host_lp_tok = torch.zeros(B, self.cap, dtype=torch.float32, pin_memory=True)
+            self.host_lp_top_v = torch.zeros(B, self.cap, W, dtype=torch.float32, pin_memory=True)
+            self.host_lp_top_i = torch.zeros(B, self.cap, W, dtype=torch.int32, pin_memory=True)
+
+    def _logprob_entries(self, host: bool, r: int, lo: int, hi: int, n: int) -> list:
+        """Columns [lo, hi) of row ``r`` as ``(logprob, [(id, logprob), ...n])`` entries."""
+        t, tv, ti = ((self.host_lp_tok, self.host_lp_top_v, self.host_lp_top_i) if host
+                     else (self.lp_tok, self.lp_top_v, self.lp_top_i))
+        lt = t[r, lo:hi].tolist()
+        vs = tv[r, lo:hi, :n].tolist()
+        ids = ti[r, lo:hi, :n].tolist()
+        return [(lt[j], list(zip(ids[j], vs[j]))) for j in range(hi - lo)]
+
+    def _copy_logprobs(self, r: int, lo: int, hi: int) -> None:
+        """Queue the host copy of columns [lo, hi) of row ``r`` (beside the token snapshot)."""
+        self.host_lp_tok[r, lo:hi].copy_(self.lp_tok[r, lo:hi], non_blocking=True)
+        self.host_lp_top_v[r, lo:hi].copy_(self.lp_top_v[r, lo:hi], non_blocking=True)
+        self.host_lp_top_i[r, lo:hi].copy_(self.lp_top_i[r, lo:hi], non_blocking=True)
 
     def _penalty_state(self) -> None:
         """Allocate the penalty history words and parameters (first penalised bind)."""
@@ -1006,6 +1069,10 @@ class Engine:
         self.top_p[r] = p.top_p
         self.seeds[r] = p.seed
         self.ln_min_p[r] = p.ln_min_p
+        if p.logprobs is not None:
+            if isinstance(p.logprobs, bool) or not 0 <= int(p.logprobs) <= LOGPROBS_WIDTH:
+                raise EngineError(f"logprobs is an int in [0, {LOGPROBS_WIDTH}], got {p.logprobs!r}")
+            self._logprob_state()
         if p.penalised:
             assert len(s.ids) == s.length, (len(s.ids), s.length)
             self._penalty_state()
@@ -1032,17 +1099,20 @@ class Engine:
 
     @torch.no_grad()
     def warmup_graphs(self, batch_sizes: Optional[List[int]] = None, topkp: bool = False,
-                      penalties: bool = False) -> int:
+                      penalties: bool = False, logprobs: bool = False) -> int:
         """Capture every decode graph this engine can need (per batch size x context bucket) up
         front. A process hosting several engines must do this before serving: a capture running
         beside another engine's work is invalidated by HIP, so serving never captures
         (``capture_on_demand`` False -> a missing graph runs eagerly). ``topkp`` / ``penalties``:
         the sampling form the graphs carry (the top-k/top-p launch; the penalty launch ahead of the
-        sampler); call once per form the process will serve."""
+        sampler); ``logprobs``: the two log-probability launches around it; call once per form the
+        process will serve."""
         if not (self.on_gpu and self.ecfg.use_graphs):
             return 0
         if penalties:
             self._penalty_state()
+        if logprobs:
+            self._logprob_state()
         self.capture_on_demand = True
         n = 0
         # TP: every rank starts its warm-up steps (eager, with collectives) together — a rank still
@@ -1052,10 +1122,10 @@ class Engine:
         with self._on_stream():
             for B in batch_sizes or list(range(1, self.ecfg.max_batch + 1)):
                 for bk in self.buckets():
-                    self._use_topkp, self._use_penalties = topkp, penalties
+                    self._use_topkp, self._use_penalties, self._use_logprobs = topkp, penalties, logprobs
                     self._graph(B, bk)
                     n += 1
-        self._use_topkp = self._use_penalties = False
+        self._use_topkp = self._use_penalties = self._use_logprobs = False
         self.capture_on_demand = False
         if self.tp.size > 1:
             self.stream.synchronize()
@@ -1066,6 +1136,8 @@ class Engine:
 
     def _graph(self, B: int, bucket: int):
         key = (B, bool(self._use_topkp), bool(self._use_penalties), bucket)
+        if self._use_logprobs:
+            key += (True,)
         g = self._graphs.get(key)
         if g is not None or not self.capture_on_demand:
             return g
@@ -1090,6 +1162,8 @@ class Engine:
               self.next_tok]
         if self._use_penalties:  # the eager warm-up step before a capture counts its tokens there
             st.append(self.pen_words[:B])
+        if self._use_logprobs:  # ... and writes a column of the rings
+            st += [self.lp_tok[:B], self.lp_top_v[:B], self.lp_top_i[:B]]
         return st
 
     def _snapshot_state(self, B: int):
@@ -1101,9 +1175,13 @@ class Engine:
 
     @torch.no_grad()
     def decode(self, seqs: List[Sequence], params: List[SamplingParams], ctx: Optional[Context] = None,
-               on_tokens: Optional[Callable[[int, List[int]], None]] = None) -> List[List[int]]:
+               on_tokens: Optional[Callable[[int, List[int]], None]] = None,
+               on_logprobs: Optional[Callable[[int, list], None]] = None) -> List[List[int]]:
         """Sample from each sequence's prefill logits, then decode until every row hits max_tokens /
-        EOS. ``on_tokens(i, new_ids)`` streams tokens (i indexes ``seqs``). Rows must be 0..B-1."""
+        EOS. ``on_tokens(i, new_ids)`` streams tokens (i indexes ``seqs``). Rows must be 0..B-1.
+        Rows whose params ask for ``logprobs`` also get ``on_logprobs(i, entries)`` right after
+        ``on_tokens`` (one entry per new token), and the returned ``Tokens`` list holds the per-row
+        entry lists in ``.logprobs`` (``None`` for a row that did not ask)."""
         B = len(seqs)
         if B > self.ecfg.max_batch:
             raise EngineError(f"{B} sequences > max_batch {self.ecfg.max_batch}")
@@ -1114,6 +1192,7 @@ class Engine:
             max_new = max(p.max_tokens for p in params)
             self._use_topkp = any(p.topkp for p in params)
             self._use_penalties = any(p.penalised for p in params)
+            self._use_logprobs = any(p.logprobs is not None for p in params)
             for i, (s, p) in enumerate(zip(seqs, params)):
                 if not s.has_logits:
                     raise EngineError("sequence has no prefill logits")
@@ -1125,7 +1204,9 @@ class Engine:
             self._sample(B, self._gather_logits(B))
             produced = [0] * B
             done = [False] * B
-            results: List[List[int]] = [[] for _ in range(B)]
+            results = Tokens([] for _ in range(B))
+            results.logprobs = [[] if p.logprobs is not None else None for p in params]
+            report = self.tp.rank == 0  # every TP rank holds the same values: only the leader reports them
             issued = 1
 
             def consume(counts, toks) -> None:
@@ -1144,6 +1225,12 @@ class Engine:
                         results[i].extend(new)
                         if on_tokens:
                             on_tokens(i, new)
+                        if results.logprobs[i] is not None and report:
+                            ent = self._logprob_entries(toks is not self.out_tokens, r, produced[i],
+                                                        produced[i] + len(new), params[i].logprobs)
+                            results.logprobs[i].extend(ent)
+                            if on_logprobs:
+                                on_logprobs(i, ent)
                     produced[i] = n if not stop else produced[i] + len(new)
                     if stop or n >= params[i].max_tokens:
                         done[i] = True
@@ -1203,6 +1290,10 @@ class Engine:
                 if hi > lo:  # per row: contiguous spans, so the copies stay asynchronous
                     for r in range(B):
                         self.host_tokens[r, lo:hi].copy_(self.out_tokens[r, lo:hi], non_blocking=True)
+                if report:  # a row's own window: a top-20 column is 40x a token's
+                    for i in range(B):
+                        if results.logprobs[i] is not None and not done[i] and hi > produced[i]:
+                            self._copy_logprobs(seqs[i].row, produced[i], hi)
                 ev = torch.cuda.Event()
                 ev.record(self.stream)
                 return ev
@@ -1417,6 +1508,7 @@ class Engine:
                 params = params or [SamplingParams(n, 0.0, 1.0, 0, 0, False)] * B
                 self._use_topkp = any(p.topkp for p in params)
                 self._use_penalties = any(p.penalised for p in params)
+                self._use_logprobs = any(p.logprobs is not None for p in params)
                 self._bind_rows(seqs, params)
                 rows = self._debug_raw_logits = [self.logits_local[:B].clone()]
                 try:
@@ -1449,24 +1541,29 @@ class Engine:
                      top_k: int = 0, seed: int = 0, stop_on_eos: bool = True, ctx: Optional[Context] = None,
                      on_tokens: Optional[Callable[[List[int]], None]] = None, min_p: float = 0.0,
                      repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
-                     frequency_penalty: float = 0.0) -> List[int]:
+                     frequency_penalty: float = 0.0, logprobs: Optional[int] = None,
+                     on_logprobs: Optional[Callable[[list], None]] = None) -> List[int]:
         seq = self.new_sequence()
         try:
             self.prefill([seq], [list(prompt)])
             p = SamplingParams(max_tokens, temperature, top_p, top_k, seed, stop_on_eos, min_p, repetition_penalty,
-                               presence_penalty, frequency_penalty)
+                               presence_penalty, frequency_penalty, logprobs)
             cb = (lambda i, ids: on_tokens(ids)) if on_tokens else None
-            return self.decode([seq], [p], ctx, cb)[0]
+            lcb = (lambda i, ent: on_logprobs(ent)) if on_logprobs else None
+            res = self.decode([seq], [p], ctx, cb, lcb)
+            out = Tokens(res[0])
+            out.logprobs = res.logprobs[0]
+            return out
         finally:
             self.free_sequence(seq)
 
     @torch.no_grad()
     def generate_batch(self, prompts: List[List[int]], params: List[SamplingParams], ctx: Optional[Context] = None,
-                       on_tokens=None) -> List[List[int]]:
+                       on_tokens=None, on_logprobs=None) -> List[List[int]]:
         seqs = [self.new_sequence() for _ in prompts]
         try:
             self.prefill(seqs, prompts)
-            return self.decode(seqs, params, ctx, on_tokens)
+            return self.decode(seqs, params, ctx, on_tokens, on_logprobs)
         finally:
             for s in seqs:
                 self.free_sequence(s)

@@ -755,6 +755,112 @@ def sample(logits, inv_temp, top_k, top_p, seeds, positions, next_tok, workspace
     return next_tok
 
 
+LOGPROBS_MAX_TOP = 20     # widest top list of token_logprobs (the OpenAI / vLLM limit)
+LOGPROBS_MAX_PART = 4096  # floats of one of the 64 vocabulary parts that stage 1 stages in LDS
+
+
+def logprobs_workspace(B: int, n_top: int, device):
+    """Part workspaces of the two log-probability launches for up to ``B`` rows: the parts' maxima and
+    sums [B, 64] and their ``n_top`` (logit, id) candidates [B, 64, n_top]."""
+    P = 64
+    f32 = dict(dtype=torch.float32, device=device)
+    return (torch.zeros(B, P, **f32), torch.zeros(B, P, **f32), torch.zeros(B, P, max(n_top, 1), **f32),
+            torch.zeros(B, P, max(n_top, 1), dtype=torch.int32, device=device))
+
+
+def _logprobs_check(logits, n_top, ws, name: str):
+    if logits.dim() != 2 or logits.dtype != torch.float32 or logits.stride(1) != 1:
+        raise TypeError(f"{name}: float32 logits [B, V] with unit column stride")
+    if isinstance(n_top, bool) or not isinstance(n_top, int) or not 0 <= n_top <= LOGPROBS_MAX_TOP:
+        raise ValueError(f"{name}: n_top is an int in [0, {LOGPROBS_MAX_TOP}], got {n_top!r}")
+    B, V = logits.shape
+    if (V + 63) // 64 > LOGPROBS_MAX_PART:
+        raise ValueError(f"{name}: a vocabulary of {V} exceeds 64 parts of {LOGPROBS_MAX_PART}")
+    pm, ps, cv, ci = ws
+    for t, dt in ((pm, torch.float32), (ps, torch.float32), (cv, torch.float32), (ci, torch.int32)):
+        if t.dtype != dt or not t.is_contiguous() or t.shape[0] < B or t.shape[1] != 64:
+            raise TypeError(f"{name}: workspace {tuple(t.shape)} {t.dtype} does not serve {B} rows")
+    if cv.numel() < B * 64 * n_top or ci.numel() < B * 64 * n_top:
+        raise ValueError(f"{name}: the candidate workspace is narrower than n_top = {n_top}")
+    return B, V
+
+
+def logprobs_stage1(logits, n_top: int, ws):
+    """First log-probability launch: per vocabulary part its maximum, its sum of exponentials and its
+    top-``n_top`` candidates, into ``ws`` (``logprobs_workspace``). It reads the raw row, so it runs
+    ahead of ``penalize_logits``. A CPU row needs no workspace: stage 2 computes from the row itself."""
+    B, V = _logprobs_check(logits, n_top, ws, "logprobs_stage1")
+    if logits.is_cuda and B > 0:
+        kernels().logprobs_stage1(_p(logits), logits.stride(0), B, V, n_top, _p(ws[0]), _p(ws[1]), _p(ws[2]),
+                                  _p(ws[3]), _s(logits))
+
+
+def logprobs_stage2(raw, tokens, n_top: int, ws, lp_tok, lp_top_v, lp_top_i, out_count=None):
+    """Second log-probability launch, after the sampler's: ``lp = l - lse`` of ``tokens[b]`` (read from
+    ``raw``, the unpenalised row) and of the row's top ``n_top``, written at column ``out_count[b] - 1``
+    of ``lp_tok`` [B, cap] and ``lp_top_v`` / ``lp_top_i`` [B, cap, >= n_top] (column 0 without
+    ``out_count``); a column outside [0, cap) is not written."""
+    B, V = _logprobs_check(raw, n_top, ws, "logprobs_stage2")
+    if tokens.dtype != torch.int32 or tokens.dim() != 1 or tokens.shape[0] < B or tokens.stride(0) != 1:
+        raise TypeError("logprobs_stage2: tokens is a contiguous int32 [B] tensor")
+    if lp_tok.dtype != torch.float32 or lp_tok.dim() != 2 or lp_tok.shape[0] < B or not lp_tok.is_contiguous():
+        raise TypeError("logprobs_stage2: lp_tok is a contiguous float32 [B, cap] tensor")
+    cap = lp_tok.shape[1]
+    for t, dt, nm in ((lp_top_v, torch.float32, "lp_top_v"), (lp_top_i, torch.int32, "lp_top_i")):
+        if (t.dtype != dt or t.dim() != 3 or t.shape[0] < B or t.shape[1] != cap or t.shape[2] < n_top
+                or t.shape[2] != lp_top_v.shape[2] or not t.is_contiguous()):
+            raise TypeError(f"logprobs_stage2: {nm} is a contiguous {dt} [B, {cap}, >= {n_top}] tensor")
+    if out_count is not None and (out_count.dtype != torch.int32 or out_count.dim() != 1 or out_count.shape[0] < B
+                                  or out_count.stride(0) != 1):
+        raise TypeError("logprobs_stage2: out_count is a contiguous int32 [B] tensor")
+    if cap <= 0 or B <= 0:
+        return
+    if not raw.is_cuda:
+        t, tv, ti = oracle.token_logprobs(raw, tokens[:B], n_top)
+        for b in range(B):
+            c = int(out_count[b]) - 1 if out_count is not None else 0
+            if 0 <= c < cap:
+                lp_tok[b, c] = t[b]
+                lp_top_v[b, c, :n_top] = tv[b]
+                lp_top_i[b, c, :n_top] = ti[b]
+        return
+    kernels().logprobs_stage2(_p(raw), raw.stride(0), B, V, n_top, _p(tokens), _p(ws[0]), _p(ws[1]), _p(ws[2]),
+                              _p(ws[3]), _p(out_count), cap, _p(lp_tok), _p(lp_top_v), _p(lp_top_i),
+                              lp_top_v.shape[2], _s(raw))
+
+
+def token_logprobs(logits, tokens, n_top: int, *, out_count=None, lp_tok=None, lp_top_v=None, lp_top_i=None,
+                   ws=None):
+    """Raw log-probabilities of ``tokens`` (int32 [B]) and of the ``n_top`` most likely ids under
+    float32 ``logits`` [B, V] (a row stride is fine), both launches back to back: the bare form, for
+    tests of the kernels alone (the engine launches the stages on either side of the sampler).
+    ``oracle.token_logprobs`` states the arithmetic and the ordering rule.
+
+    Without buffers it returns ``(lp_tok [B], top_v [B, n_top], top_i [B, n_top])``. With ``lp_tok``
+    [B, cap], ``lp_top_v`` / ``lp_top_i`` [B, cap, >= n_top] (and ``out_count``, the decode state's
+    token counts) it writes column ``out_count[b] - 1`` of them, as a decode step does, and returns
+    the three buffers."""
+    B = logits.shape[0]
+    dev = logits.device
+    if ws is None:
+        ws = logprobs_workspace(B, n_top if isinstance(n_top, int) else 0, dev)
+    bare = lp_tok is None
+    if bare:
+        if lp_top_v is not None or lp_top_i is not None or out_count is not None:
+            raise ValueError("token_logprobs: out_count and the top buffers come with lp_tok")
+        _logprobs_check(logits, n_top, ws, "token_logprobs")
+        lp_tok = torch.zeros(B, 1, dtype=torch.float32, device=dev)
+        lp_top_v = torch.zeros(B, 1, n_top, dtype=torch.float32, device=dev)
+        lp_top_i = torch.zeros(B, 1, n_top, dtype=torch.int32, device=dev)
+    elif lp_top_v is None or lp_top_i is None:
+        raise ValueError("token_logprobs: lp_tok comes with lp_top_v and lp_top_i")
+    logprobs_stage1(logits, n_top, ws)
+    logprobs_stage2(logits, tokens, n_top, ws, lp_tok, lp_top_v, lp_top_i, out_count)
+    if bare:
+        return lp_tok[:, 0], lp_top_v[:, 0], lp_top_i[:, 0]
+    return lp_tok, lp_top_v, lp_top_i
+
+
 def _advance_cpu(tok, tokens_in, positions, seq_lens, slots, block_tables, bs, out_tokens, out_count):
     if tokens_in is None:
         return

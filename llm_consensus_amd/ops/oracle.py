@@ -292,6 +292,31 @@ def sample(logits: torch.Tensor, inv_temp, top_k, top_p, seeds, positions, *, wo
     return out, counted
 
 
+def token_logprobs(logits: torch.Tensor, tokens: torch.Tensor, n_top: int):
+    """Raw log-probabilities of float32 ``logits`` [B, V]: ``lp = l - lse`` with
+    ``lse = M + ln(sum exp(l - M))`` in float32, M the row maximum, NaN entries left out of the sum and
+    of the ranking. Returns ``(lp_tok [B], top_v [B, n_top], top_i [B, n_top] int32)``: the value of
+    ``tokens[b]`` and the ``n_top`` most likely ids ordered by (logit descending, id ascending); places
+    past the comparable entries hold id -1 and -inf."""
+    B, V = logits.shape
+    lp_tok = torch.empty(B, dtype=torch.float32)
+    top_v = torch.full((B, n_top), -math.inf, dtype=torch.float32)
+    top_i = torch.full((B, n_top), -1, dtype=torch.int32)
+    for b in range(B):
+        row = logits[b].float()
+        ok = ~torch.isnan(row)
+        ids = torch.nonzero(ok).flatten()
+        vals = row[ids]
+        M = vals.max() if ids.numel() else torch.tensor(-math.inf)
+        lse = M + torch.log(torch.exp(vals - M).sum()) if M > -math.inf else M
+        lp_tok[b] = row[int(tokens[b])] - lse
+        order = torch.sort(vals, descending=True, stable=True).indices[:n_top]  # stable: ties keep the smaller id
+        k = order.numel()
+        top_v[b, :k] = vals[order] - lse
+        top_i[b, :k] = ids[order].to(torch.int32)
+    return lp_tok, top_v, top_i
+
+
 # -- MoE ------------------------------------------------------------------------------------------
 def moe_route(logits: torch.Tensor, k: int):
     p = torch.softmax(logits.float(), dim=-1)

@@ -28,6 +28,8 @@ class Result:
     judge: str
     warnings: Optional[List[str]] = None
     failed_models: Optional[List[str]] = None
+    # Non-schema (never in result.json): ``logprobs_object`` of a run that asked for log-probabilities
+    logprobs: Optional[dict] = None
 
 
 def go_string(s: str) -> str:
@@ -74,3 +76,31 @@ def encode_result(res: Result) -> str:
     if res.failed_models:
         fields.append('  "failed_models": ' + _str_array(res.failed_models, "  "))
     return "{\n" + ",\n".join(fields) + "\n}\n"
+
+
+def logprobs_object(responses: List[Response], judge: Optional[Response]) -> dict:
+    """``{"responses": {model: [...]}, "judge": [...]}``: every response's per-token entries
+    (``Response.logprobs``; ``[]`` for a provider that reports none) and the judge's."""
+    return {"responses": {r.model: r.logprobs or [] for r in responses},
+            "judge": (judge.logprobs or []) if judge is not None else []}
+
+
+def logprob_summary(entries: list) -> dict:
+    """Token count, mean log-probability and perplexity (exp of minus the mean) of one output."""
+    import math
+
+    vals = [e["logprob"] for e in entries if e.get("logprob") is not None]
+    if not vals:
+        return {"tokens": len(entries), "mean_logprob": None, "perplexity": None}
+    mean = sum(vals) / len(vals)
+    return {"tokens": len(entries), "mean_logprob": mean, "perplexity": math.exp(-mean)}
+
+
+def encode_result_with_logprobs(res: Result) -> str:
+    """``encode_result`` with one extra, last key ``"logprobs"`` (the server's non-streaming reply to a
+    request that asked)."""
+    import json
+
+    text = encode_result(res)
+    assert text.endswith("\n}\n")
+    return text[:-3] + ',\n  "logprobs": ' + json.dumps(res.logprobs) + "\n}\n"

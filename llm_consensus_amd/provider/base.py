@@ -38,9 +38,16 @@ class Request:
     repetition_penalty: Optional[float] = None
     presence_penalty: Optional[float] = None
     frequency_penalty: Optional[float] = None
+    # token log-probabilities (local engines): None = off, n in [0, 20] = the sampled token's raw
+    # log-probability and the n most likely ids of every step (``Response.logprobs``)
+    logprobs: Optional[int] = None
 
 
-def check_sampling(min_p=None, repetition_penalty=None, presence_penalty=None, frequency_penalty=None) -> None:
+MAX_LOGPROBS = 20
+
+
+def check_sampling(min_p=None, repetition_penalty=None, presence_penalty=None, frequency_penalty=None,
+                   logprobs=None) -> None:
     """Raise ValueError("<name>: <why>") for a value no engine may see (``None`` = not given)."""
     def num(name, v):
         if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
@@ -58,6 +65,11 @@ def check_sampling(min_p=None, repetition_penalty=None, presence_penalty=None, f
         num("presence_penalty", presence_penalty)
     if frequency_penalty is not None:
         num("frequency_penalty", frequency_penalty)
+    if logprobs is not None:
+        if isinstance(logprobs, bool) or not isinstance(logprobs, int):
+            raise ValueError(f"logprobs: expected an integer, got {logprobs!r}")
+        if not 0 <= logprobs <= MAX_LOGPROBS:
+            raise ValueError(f"logprobs: expected a value in [0, {MAX_LOGPROBS}], got {logprobs!r}")
 
 
 @dataclasses.dataclass
@@ -70,6 +82,9 @@ class Response:
     prompt_tokens: int = 0
     output_tokens: int = 0
     ttft_ns: int = 0
+    # None unless the request asked for ``logprobs``: one {"id", "token", "logprob", "top": [{"id",
+    # "token", "logprob"}, ...]} per output token (raw values: before penalties, temperature, truncation)
+    logprobs: Optional[list] = None
 
     @property
     def latency_ms(self) -> int:

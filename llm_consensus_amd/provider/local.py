@@ -18,6 +18,7 @@ last block's remainder and the trailer are prefilled before decoding.
 from __future__ import annotations
 
 import itertools
+import math
 import os
 import queue
 import socket
@@ -269,7 +270,10 @@ class LocalBackend:
                                    # launch forms (ops.attn_oproj_min_chunk)
                                    "alone": alone[m],
                                    # (top-k/top-p launch, penalty launch) of the run's requests
-                                   "sampling_form": sampling_form(sampling, s.config, self.model_sampling)})
+                                   "sampling_form": sampling_form(sampling, s.config, self.model_sampling),
+                                   # whether the run's requests ask for log-probabilities: the workers
+                                   # then capture that form of the decode graphs too
+                                   "logprobs": sampling is not None and sampling.logprobs is not None})
             if groups:
                 dist_info = {"port": port, "rank": rank_of[g], "world": len(used),
                              "groups": [(m, [rank_of[x] for x in gs]) for m, gs in groups]}
@@ -384,12 +388,21 @@ class LocalProvider:
         out = sampling_knobs(req, self.spec.config, self.backend.model_sampling)
         out.update({"max_tokens": int(mt), "seed": int(seed),
                     "stop_on_eos": True if req.stop_on_eos is None else bool(req.stop_on_eos)})
+        if req.logprobs is not None:  # requests that do not ask send today's params
+            out["logprobs"] = int(req.logprobs)
         return out
 
+    def _logprob_pair(self, i: int, lp: float) -> dict:
+        """{"id", "token", "logprob"} of one id: ``token`` is the tokenizer's text of that single id."""
+        # JSON has no -inf: an id whose logit is masked (or an empty place, id -1) reports null
+        return {"id": int(i), "token": self.tok.decode([int(i)]) if i >= 0 else "",
+                "logprob": float(lp) if math.isfinite(lp) else None}
+
     def _stream(self, ctx: Context, rid: int, q: "queue.Queue", callback: Optional[StreamCallback], t0: int,
-                prompt_tokens: int) -> Response:
+                prompt_tokens: int, want_logprobs: bool = False) -> Response:
         dec = self.tok.stream_decoder()
         parts: List[str] = []
+        lps: Optional[list] = [] if want_logprobs else None
         ntok = 0
         ttft = 0
         try:
@@ -414,6 +427,11 @@ class LocalProvider:
                         parts.append(chunk)
                         if callback is not None:
                             callback(chunk)
+                elif kind == "logprobs":  # follows the "tokens" message it belongs to
+                    for tid, lp, top in msg[2]:
+                        e = self._logprob_pair(tid, lp)
+                        e["top"] = [self._logprob_pair(i, v) for i, v in top]
+                        lps.append(e)
                 elif kind == "done":
                     break
                 elif kind == "error":
@@ -427,7 +445,7 @@ class LocalProvider:
             self.backend._end_request(rid)
         return Response(model=self.model, content="".join(parts), provider=self.provider_name,
                         latency_ns=time.monotonic_ns() - t0, prompt_tokens=prompt_tokens, output_tokens=ntok,
-                        ttft_ns=ttft)
+                        ttft_ns=ttft, logprobs=lps)
 
     # -- Provider API -------------------------------------------------------------------------------
     def query(self, ctx: Context, req: Request) -> Response:
@@ -440,7 +458,7 @@ class LocalProvider:
         rid, q = self.backend._new_request(self.model)
         with tracing.span("query", cat="driver", model=self.model, prompt_tokens=len(ids)):
             self.backend.broadcast(self.model, ("generate", rid, self.model, ids, params))
-            return self._stream(ctx, rid, q, callback, t0, len(ids))
+            return self._stream(ctx, rid, q, callback, t0, len(ids), "logprobs" in params)
 
     # -- judge sessions (incremental prefill) ---------------------------------------------------------
     def new_session(self, header: str) -> "JudgeSession":
@@ -541,4 +559,4 @@ class JudgeSession:
         with tracing.span("judge_session_finish", cat="driver", model=p.model, rest_tokens=len(rest),
                           reused_tokens=cp):
             p.backend.broadcast(p.model, ("sess_generate", self.sid, rid, rest, params, cp))
-            return p._stream(ctx, rid, q, callback, t0, len(full))
+            return p._stream(ctx, rid, q, callback, t0, len(full), "logprobs" in params)

@@ -7,6 +7,8 @@ Control plane (C6): a duplex pipe to the driver carrying commands and token-id s
                     ("cancel", rid) / ("shutdown",)
   worker -> driver  ("ready", info) / ("fatal", msg)
                     ("tokens", rid, ids) / ("done", rid, stats) / ("error", rid, msg)
+                    ("logprobs", rid, [(id, logprob, [(id, logprob), ...]), ...]) right after the
+                    "tokens" message it belongs to, for requests whose params carry "logprobs"
 Each engine has its own thread, hipStream and FIFO work queue, so engines co-located on a GPU
 (responders + judge, config 3) run concurrently, and requests for the same engine are BATCHED
 into one decode (replica batching: up to ``max_batch`` rows share every weight read).
@@ -203,7 +205,10 @@ class _EngineHost:
             sent[req.rid] = sent.get(req.rid, 0) + len(ids)
             self._emit("tokens", req.rid, ids)
 
-        bat = ContinuousBatcher(self.engine, on_tokens)
+        def on_logprobs(row, ent):
+            self._emit("logprobs", row.tag[0].rid, [(t, lp, top) for t, (lp, top) in zip(row.tokens[-len(ent):], ent)])
+
+        bat = ContinuousBatcher(self.engine, on_tokens, on_logprobs)
         waiting: "deque" = deque()
         stop = False
 
@@ -341,6 +346,7 @@ class _EngineHost:
         params = [SP(**r.params) for r in reqs]
         first = [0] * len(reqs)
         sent = [0] * len(reqs)
+        last: List[list] = [[] for _ in reqs]  # the ids of the "tokens" message a "logprobs" one follows
 
         def on_tokens(i, ids):
             if not first[i]:
@@ -349,11 +355,15 @@ class _EngineHost:
                 raise InjectedFault(f"injected fault: {self.name} decode after {k} tokens")
             sent[i] += len(ids)
             self._emit("tokens", reqs[i].rid, ids)
+            last[i] = ids
+
+        def on_logprobs(i, ent):
+            self._emit("logprobs", reqs[i].rid, [(t, lp, top) for t, (lp, top) in zip(last[i], ent)])
 
         # a batch is cancelled only if every member is; single requests use their own context
         ctx = reqs[0].ctx if len(reqs) == 1 else _AllCtx([r.ctx for r in reqs])
         del Context
-        outs = self.engine.decode(seqs, params, ctx, on_tokens)
+        outs = self.engine.decode(seqs, params, ctx, on_tokens, on_logprobs)
         t1 = time.monotonic_ns()
         for i, r in enumerate(reqs):
             self._emit("done", r.rid, {"prompt_tokens": len(prompts[i]), "output_tokens": len(outs[i]),
@@ -431,6 +441,7 @@ def worker_main(gpu: int, conn, models: List[dict], dist_info: Optional[dict], t
         ctxs: Dict[int, Context] = {}  # live requests' contexts (cancel); dropped when they finish
         faults = parse_faults(os.environ.get("LLMC_FAULT", ""))
         forms = {m["name"]: tuple(m.get("sampling_form") or (False, False)) for m in models}
+        want_lp = {m["name"]: bool(m.get("logprobs")) for m in models}
         for m in models:
             cfg = FAMILIES.get(m["family"])
             if cfg is None and m.get("checkpoint"):  # --weights-dir family (spawned: re-register)
@@ -474,6 +485,8 @@ def worker_main(gpu: int, conn, models: List[dict], dist_info: Optional[dict], t
                     topkp, pen = forms.get(h.name, (False, False))
                     if topkp or pen:
                         h.engine.warmup_graphs(topkp=topkp, penalties=pen)
+                    if want_lp.get(h.name):
+                        h.engine.warmup_graphs(topkp=topkp, penalties=pen, logprobs=True)
             torch.cuda.synchronize()
         send(("ready", {"gpu": gpu, "models": list(hosts)}))
     except Exception as e:  # noqa: BLE001

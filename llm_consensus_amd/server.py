@@ -41,7 +41,7 @@ from typing import Callable, List, Optional
 
 from .consensus import Judge, prompt_header, response_block
 from .context import Context
-from .output import Result, encode_result
+from .output import Result, encode_result, encode_result_with_logprobs, logprobs_object
 from .provider.base import Request, Response, check_sampling
 from .runner import Callbacks, Runner
 
@@ -89,23 +89,23 @@ class ConsensusService:
                  concurrency: int = 4, timeout: float = 120.0, max_tokens: int = 0, temperature: float = 1.0,
                  top_p: float = 1.0, top_k: int = 0, seed: int = 0, min_p: float = 0.0,
                  repetition_penalty: float = 1.0, presence_penalty: float = 0.0, frequency_penalty: float = 0.0,
-                 model_sampling: bool = False):
+                 model_sampling: bool = False, logprobs: Optional[int] = None):
         from .cli import Config, init_registry
 
         pen = dict(min_p=min_p, repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
                    frequency_penalty=frequency_penalty)
-        check_sampling(**pen)  # before any engine starts
+        check_sampling(**pen, logprobs=logprobs)  # before any engine starts
 
         self.responders = list(dict.fromkeys(models))
         self.judge = judge
         self.timeout = timeout
         self.concurrency = max(1, concurrency)
         self.defaults = dict(max_tokens=max_tokens, temperature=temperature, top_p=top_p, top_k=top_k, seed=seed,
-                             **pen)
+                             logprobs=logprobs, **pen)
         cfg = Config(models=self.responders, judge=judge, file="", output="", data_dir="", timeout=timeout,
                      prompt="", quiet=True, json=True, no_save=True, max_tokens=max_tokens,
                      temperature=temperature, top_p=top_p, top_k=top_k, seed=seed, gpus=gpus, trace=False,
-                     placement=placement, judge_tp=judge_tp, model_sampling=model_sampling, **pen)
+                     placement=placement, judge_tp=judge_tp, model_sampling=model_sampling, logprobs=logprobs, **pen)
         self.registry = init_registry(cfg, concurrency=self.concurrency)
         self.served = self.registry.models()
         self._slots = threading.BoundedSemaphore(self.concurrency)
@@ -148,12 +148,15 @@ class ConsensusService:
         d = self.defaults
         pen = {k: self._param(body, k, float, d[k])
                for k in ("min_p", "repetition_penalty", "presence_penalty", "frequency_penalty")}
+        lp = body.get("logprobs", None)
+        lp = d["logprobs"] if lp is None else lp
         try:
-            check_sampling(**pen)
+            check_sampling(**pen, logprobs=lp)
         except ValueError as e:
             raise BadRequest(str(e)) from None
         return {
             **pen,
+            "logprobs": lp,
             "prompt": prompt, "models": models, "judge": judge,
             "timeout": self._param(body, "timeout", float, self.timeout),
             "max_tokens": self._param(body, "max_tokens", int, d["max_tokens"]),
@@ -190,7 +193,8 @@ class ConsensusService:
                        top_p=req["top_p"], top_k=req["top_k"] or None, seed=req["seed"] or None,
                        stop_on_eos=req.get("stop_on_eos"), min_p=req.get("min_p"),
                        repetition_penalty=req.get("repetition_penalty"), presence_penalty=req.get("presence_penalty"),
-                       frequency_penalty=req.get("frequency_penalty"))
+                       frequency_penalty=req.get("frequency_penalty"), logprobs=req.get("logprobs"))
+        want_lp = req.get("logprobs") is not None
         jp = self.registry.get(judge_name)
         session = None
         if hasattr(jp, "new_session") and len(models) > 1 and judge_name == self.judge:
@@ -200,7 +204,7 @@ class ConsensusService:
             if session is not None:
                 session.extend(response_block(r))
             ev("model_done", {"model": r.model, "provider": r.provider, "latency_ms": r.latency_ms,
-                              "output_tokens": r.output_tokens})
+                              "output_tokens": r.output_tokens, **({"logprobs": r.logprobs or []} if want_lp else {})})
 
         runner = Runner(self.registry, req["timeout"], tmpl).with_callbacks(Callbacks(
             on_model_start=lambda m: ev("model_start", {"model": m}),
@@ -225,9 +229,11 @@ class ConsensusService:
             raise ServiceError(f"consensus synthesis: {e}") from None
         if jw is not None and jw.response is not None:
             ev("judge_done", {"output_tokens": jw.response.output_tokens, "prompt_tokens": jw.response.prompt_tokens,
-                              "latency_ms": jw.response.latency_ms})
+                              "latency_ms": jw.response.latency_ms,
+                              **({"logprobs": jw.response.logprobs or []} if want_lp else {})})
         return Result(prompt=prompt, responses=result.responses, consensus=consensus, judge=judge_name,
-                      warnings=result.warnings, failed_models=result.failed_models)
+                      warnings=result.warnings, failed_models=result.failed_models,
+                      logprobs=logprobs_object(result.responses, judge.last_response) if want_lp else None)
 
 
 def _sse(name: str, payload: str) -> bytes:
@@ -291,7 +297,8 @@ def make_handler(service: ConsensusService):
                 except ServiceError as e:
                     self._json(502, {"error": str(e)})
                     return
-                self._send(200, encode_result(res).encode("utf-8", "surrogateescape"))
+                text = encode_result(res) if res.logprobs is None else encode_result_with_logprobs(res)
+                self._send(200, text.encode("utf-8", "surrogateescape"))
                 return
             # streaming: events are written by the runner's threads as they happen
             self.send_response(200)
@@ -360,6 +367,8 @@ def main(argv: Optional[List[str]] = None) -> int:
     ap.add_argument("--repetition-penalty", type=float, default=1.0)
     ap.add_argument("--presence-penalty", type=float, default=0.0)
     ap.add_argument("--frequency-penalty", type=float, default=0.0)
+    ap.add_argument("--logprobs", type=int, default=None,
+                    help="default for requests: report token log-probabilities with N alternatives (0-20)")
     ap.add_argument("--model-sampling", action="store_true",
                     help="checkpoint models sample with their generation_config.json values where a knob is neutral")
     ap.add_argument("--gpus", default="")
@@ -370,7 +379,7 @@ def main(argv: Optional[List[str]] = None) -> int:
     t0 = time.monotonic()
     try:
         check_sampling(min_p=a.min_p, repetition_penalty=a.repetition_penalty, presence_penalty=a.presence_penalty,
-                       frequency_penalty=a.frequency_penalty)
+                       frequency_penalty=a.frequency_penalty, logprobs=a.logprobs)
     except ValueError as e:
         ap.error(str(e))
     svc = ConsensusService([m.strip() for m in a.models.split(",") if m.strip()], a.judge, gpus=a.gpus,
@@ -378,7 +387,7 @@ def main(argv: Optional[List[str]] = None) -> int:
                            timeout=a.timeout, max_tokens=a.max_tokens, temperature=a.temperature, top_p=a.top_p,
                            top_k=a.top_k, seed=a.seed, min_p=a.min_p, repetition_penalty=a.repetition_penalty,
                            presence_penalty=a.presence_penalty, frequency_penalty=a.frequency_penalty,
-                           model_sampling=a.model_sampling)
+                           model_sampling=a.model_sampling, logprobs=a.logprobs)
 
     def ready(port: int) -> None:
         sys.stderr.write(f"llm-consensus server: {len(svc.served)} models ready in {time.monotonic() - t0:.1f}s, "
