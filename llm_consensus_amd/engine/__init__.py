@@ -1,1 +1,2 @@
-from .engine import Engine, EngineConfig, EngineError, SamplingParams, Sequence  # noqa: F401
+from .engine import (Engine, EngineConfig, EngineError, GraphKey, SamplingForm, SamplingParams,  # noqa: F401
+                     Sequence)

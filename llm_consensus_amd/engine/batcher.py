@@ -23,7 +23,7 @@ from typing import Callable, List, Optional
 
 import torch
 
-from .engine import Engine, EngineError, SamplingParams, Sequence
+from .engine import Engine, EngineError, SamplingForm, SamplingParams, Sequence
 
 TokenFn = Callable[["Row", List[int]], None]
 
@@ -60,9 +60,6 @@ class ContinuousBatcher:
         self._host_fault = (torch.zeros(1, dtype=torch.int32, pin_memory=True) if engine.on_gpu
                             else torch.zeros(1, dtype=torch.int32))
         self._eos = set(engine.cfg.eos)
-        e = engine
-        self._row_state = [e.tokens_in, e.positions, e.seq_lens, e.slots, e.block_tables, e.out_tokens,
-                           e.out_count, e.next_tok, e.inv_temp, e.top_k, e.top_p, e.seeds, e.ln_min_p]
 
     @property
     def free_rows(self) -> int:
@@ -83,14 +80,10 @@ class ContinuousBatcher:
         e._reserve(seq, seq.length + params.max_tokens + 2 * S + 1)
         r = len(self.rows)
         with e._on_stream():
+            e._ensure_form_state(params.form)
             e.block_tables[r:r + 1].copy_(e._block_table([seq]))
-            e.logits_local[r].copy_(seq.logits)
-            e._bind_sampling(r, seq, params)  # a penalised row: its history words zeroed and seeded
-            e.positions[r] = seq.length - 1
-            e.out_count[r] = 0
-            e._use_topkp, e._use_penalties = params.topkp, params.penalised
-            e._use_logprobs = params.logprobs is not None
-            e._sample(1, e.logits_local[r:r + 1], r0=r)
+            e._bind_row(r, seq, params)  # a penalised row: its history words zeroed and seeded
+            e._sample(1, e.logits_local[r:r + 1], params.form, r0=r)
         seq.row = r
         row = Row(seq, params, tag, ctx)
         self.rows.append(row)
@@ -136,28 +129,18 @@ class ContinuousBatcher:
             if stop or n >= p.max_tokens:
                 row.done = True
 
-    def _penalty_state(self) -> list:
-        """The rows' penalty history words and parameters, once the engine holds them."""
-        e = self.e
-        return [] if e.pen_words is None else [e.pen_words, e.pen_rep, e.pen_freq, e.pen_pres]
-
     def _compact(self) -> List[Row]:
         """Drop finished rows; the live rows behind them move down (device row copies)."""
         keep = [r for r in self.rows if not r.done]
         gone = [r for r in self.rows if r.done]
         if not gone:
             return []
-        with self.e._on_stream():
-            for t, row in enumerate(keep):
-                s = row.seq.row
-                if s != t:
-                    for buf in self._row_state + self._penalty_state():
-                        buf[t].copy_(buf[s])
-                    if row.logprobs is not None:  # the columns not yet consumed travel with the row
-                        for buf in (self.e.lp_tok, self.e.lp_top_v, self.e.lp_top_i):
-                            hi = min(self.e.cap, row.issued)
-                            buf[t, row.produced:hi].copy_(buf[s, row.produced:hi])
-                    row.seq.row = t
+        for t, row in enumerate(keep):
+            if row.seq.row != t:
+                # the log-probability columns not yet consumed travel with the row
+                cols = (row.produced, min(self.e.cap, row.issued)) if row.logprobs is not None else None
+                self.e.move_row(t, row.seq.row, cols)
+                row.seq.row = t
         self.rows = keep
         for row in gone:
             row.seq.length = row.base + len(row.tokens)
@@ -177,15 +160,14 @@ class ContinuousBatcher:
         with e._on_stream():
             if need and B:
                 bucket = e._bucket(max(r.base + r.issued for r in self.rows) + S + 1)
-                e._use_topkp = any(r.params.topkp for r in self.rows)
-                e._use_penalties = any(r.params.penalised for r in self.rows)
-                e._use_logprobs = any(r.params.logprobs is not None for r in self.rows)
-                graph = e._graph(B, bucket) if (e.on_gpu and e.ecfg.use_graphs) else None
+                form = SamplingForm.of(r.params for r in self.rows)
+                e._ensure_form_state(form)  # e.g. the raw rows' copy: one row penalised, another with logprobs
+                graph = e._graph(B, bucket, form) if (e.on_gpu and e.ecfg.use_graphs) else None
                 if graph is not None:
                     graph.replay()
                 else:
                     for _ in range(S):
-                        e._decode_step(B, bucket)
+                        e._decode_step(B, form, bucket)
                 for r in self.rows:
                     r.issued += S
             if not e.on_gpu:

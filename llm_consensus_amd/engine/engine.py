@@ -24,7 +24,7 @@ import logging
 import math
 import os
 import time
-from typing import Callable, Dict, List, Optional, Sequence as Seq
+from typing import Callable, Dict, List, NamedTuple, Optional, Sequence as Seq
 
 import torch
 
@@ -35,6 +35,7 @@ from ..models.transformer import TransformerWeights
 from ..ops import EPI_BF16, EPI_F32, EPI_RESADD, EPI_SILU, oracle
 from ..parallel.comm import TPGroup
 from ..parallel.placement import packed_weights_mode
+from ..sampling import SamplingForm, SamplingParams  # noqa: F401 - the engine's public names
 from ..utils import trace
 from ..utils.native import runtime
 
@@ -200,37 +201,12 @@ def split_blocks_per_head(nh: int, nkv: int) -> int:
     return max(1, min(blocks // nkv, 256))
 
 
-@dataclasses.dataclass
-class SamplingParams:
-    max_tokens: int = 256
-    temperature: float = 1.0
-    top_p: float = 1.0
-    top_k: int = 0
-    seed: int = 0
-    stop_on_eos: bool = True
-    # sampled rows keep a token only if its probability is >= min_p x the most likely token's (0 = off)
-    min_p: float = 0.0
-    # over the ids of the context and the ids generated so far: l = l > 0 ? l / r : l * r (1 = off)
-    repetition_penalty: float = 1.0
-    # over the ids generated so far: l -= presence_penalty + frequency_penalty x (times generated)
-    presence_penalty: float = 0.0
-    frequency_penalty: float = 0.0
-    # None = off; n in [0, 20]: report the raw log-probability of every generated token and of the n
-    # most likely ids at its step (before penalties, temperature and truncation)
-    logprobs: Optional[int] = None
+class GraphKey(NamedTuple):
+    """Key of a captured decode graph: decode rows, attention bucket, sampling form."""
 
-    @property
-    def penalised(self) -> bool:
-        return self.repetition_penalty != 1.0 or self.presence_penalty != 0.0 or self.frequency_penalty != 0.0
-
-    @property
-    def topkp(self) -> bool:
-        """Whether the row needs the top-k/top-p launch (which also applies min-p)."""
-        return self.top_k > 0 or self.top_p < 1.0 or self.min_p > 0.0
-
-    @property
-    def ln_min_p(self) -> float:
-        return math.log(self.min_p) if self.min_p > 0.0 else float("-inf")
+    rows: int
+    bucket: int
+    form: SamplingForm
 
 
 LOGPROBS_WIDTH = 20  # places of the device top lists: the form is launch-uniform, rows truncate on the host
@@ -323,7 +299,7 @@ class Engine:
         self._alloc_decode_buffers()
         with self._on_stream():
             self._build_packed_weights()
-        self._graphs: Dict[int, "torch.cuda.CUDAGraph"] = {}
+        self._graphs: Dict[GraphKey, "torch.cuda.CUDAGraph"] = {}
         self._next_sid = 0
 
     # ------------------------------------------------------------------------------------------
@@ -405,12 +381,12 @@ class Engine:
         self.seeds = torch.zeros(B, dtype=torch.int64, device=dev)
         # log(min_p) per row for the top-k/top-p launch (-inf = off)
         self.ln_min_p = torch.full((B,), float("-inf"), dtype=torch.float32, device=dev)
-        # sampling penalties: history words [B, V] and the rows' parameters, allocated by the first
-        # penalised bind (_penalty_state); an engine that never sees a penalty never holds them
+        # sampling penalties: history words [B, V] and the rows' parameters, allocated for the first
+        # form with penalties (_ensure_form_state); an engine that never sees a penalty never holds them
         self.pen_words: Optional[torch.Tensor] = None
         self.pen_rep = self.pen_freq = self.pen_pres = None
-        # token log-probabilities: the rings, the part workspaces and the host twins, allocated by the
-        # first bind that asks (_logprob_state)
+        # token log-probabilities: the rings, the part workspaces and the host twins, allocated for the
+        # first form that asks; lp_raw (the raw rows' copy) for the first that also has penalties
         self.lp_tok = self.lp_top_v = self.lp_top_i = self.lp_ws = self.lp_raw = None
         self.host_lp_tok = self.host_lp_top_v = self.host_lp_top_i = None
         bf = dict(dtype=torch.bfloat16, device=dev)
@@ -801,8 +777,9 @@ class Engine:
         ops.moe_combine(y_back, w, ids, hs, rows=slot)
 
     # -- decode -------------------------------------------------------------------------------------
-    def _decode_step(self, B: int, bucket: Optional[int] = None) -> None:
-        """One token for rows 0..B-1. ``bucket`` indexes ``attn_buckets`` (default: the largest)."""
+    def _decode_step(self, B: int, form: SamplingForm, bucket: Optional[int] = None) -> None:
+        """One token for rows 0..B-1, sampled in ``form``. ``bucket`` indexes ``attn_buckets`` (default:
+        the largest)."""
         c = self.cfg
         _, chunk, grid_chunks, fused = self.attn_buckets[-1 if bucket is None else bucket]
         part = self.attn_part
@@ -852,7 +829,7 @@ class Engine:
                 self._row_parallel(act, Lw.w_down, h, Lw.p_down if pk else None)
         if dbg is not None:
             dbg.append(h.clone())
-        self._lm_head_sample(B)
+        self._lm_head_sample(B, form)
 
     _debug_layer_io: Optional[list] = None
 
@@ -887,13 +864,14 @@ class Engine:
             with self._on_stream():
                 self.prefill([seq], [list(prompt)])
                 self._reserve(seq, seq.length + 4)
-                self._use_topkp = self._use_penalties = self._use_logprobs = False
+                form = SamplingForm()
+                self._ensure_form_state(form)
                 self._bind_rows([seq], [SamplingParams(2, 0.0, 1.0, 0, 0, False)])
-                self._sample(1, self._gather_logits(1))  # the prefill's token -> this step's input
+                self._sample(1, self._gather_logits(1), form)  # the prefill's token -> this step's input
                 pos = int(self.positions[0].item())
                 self._debug_layer_io = []
                 try:
-                    self._decode_step(1, self._bucket(seq.length + 4))
+                    self._decode_step(1, form, self._bucket(seq.length + 4))
                     hs = torch.cat(self._debug_layer_io)
                 finally:
                     self._debug_layer_io = None
@@ -903,14 +881,14 @@ class Engine:
         finally:
             self.free_sequence(seq)
 
-    def _lm_head_sample(self, B: int) -> None:
+    def _lm_head_sample(self, B: int, form: SamplingForm) -> None:
         lg = self.logits_local[:B]
         ops.linear(self.h[:B], self.w.lm_head, EPI_F32, out=lg, norm_w=self.w.final_norm, eps=self.cfg.rms_eps,
                    mfma=self.mfma_decode, Wp=self.w.p_lm_head if self.packed else None)
         logits = self._gather_logits(B)
         if self._debug_raw_logits is not None:  # eager debug steps only: the row before any penalty
             self._debug_raw_logits.append(logits.clone())
-        self._sample(B, logits)
+        self._sample(B, logits, form)
 
     _debug_raw_logits: Optional[list] = None
 
@@ -986,54 +964,57 @@ class Engine:
             torch.cuda.current_stream(self.device).wait_stream(self.stream)
         return out
 
-    def _sample(self, B: int, logits: torch.Tensor, r0: int = 0) -> None:
-        """Sample rows r0 .. r0 + B - 1 from ``logits`` [B, V] and advance their state. With
-        ``_use_penalties`` the rows are penalised first from their history words (a launch of its
+    def _sample(self, B: int, logits: torch.Tensor, form: SamplingForm, r0: int = 0) -> None:
+        """Sample rows r0 .. r0 + B - 1 from ``logits`` [B, V] in ``form`` and advance their state. With
+        ``form.penalties`` the rows are penalised first from their history words (a launch of its
         own) and the advance counts the sampled ids there; every rank of a TP group holds the full
-        table and penalises the gathered row, so the ranks sample the same token and stay equal."""
-        use_topkp = bool(self._use_topkp)
+        table and penalises the gathered row, so the ranks sample the same token and stay equal.
+        Allocates nothing (it runs inside graph captures): ``_ensure_form_state(form)`` came first."""
         sl = slice(r0, r0 + B)
         pen = {}
-        if self._use_penalties:
+        if form.penalties:
             pen = dict(words=self.pen_words[sl], rep=self.pen_rep[sl], freq=self.pen_freq[sl], pres=self.pen_pres[sl])
         raw = logits
-        if self._use_logprobs:
+        if form.logprobs:
             # stage 1 reads the raw row, so it runs ahead of the penalty launch; stage 2 runs after the
             # sampler and needs the raw row again for the sampled id: a copy when penalties rewrite it
             ops.logprobs_stage1(logits, LOGPROBS_WIDTH, self.lp_ws)
-            if self._use_penalties:
-                if self.lp_raw is None:  # an eager step always comes first (decode's first token, a warm-up)
-                    self.lp_raw = torch.zeros(self.ecfg.max_batch, self.cfg.vocab, dtype=torch.float32,
-                                              device=self.device)
+            if form.penalties:
                 raw = self.lp_raw[:B]
                 raw.copy_(logits)
         ops.sample(logits, self.inv_temp[sl], self.top_k[sl], self.top_p[sl], self.seeds[sl], self.positions[sl],
                    self.next_tok[sl], self.ws_v[sl] if self.ws_v is not None else None,
                    self.ws_i[sl] if self.ws_i is not None else None, tokens_in=self.tokens_in[sl],
                    seq_lens=self.seq_lens[sl], slots=self.slots[sl], block_tables=self.block_tables[sl], bs=self.bs,
-                   out_tokens=self.out_tokens[sl], out_count=self.out_count[sl], use_topkp=use_topkp,
+                   out_tokens=self.out_tokens[sl], out_count=self.out_count[sl], use_topkp=form.topkp,
                    ln_min_p=self.ln_min_p[sl], **pen)
-        if self._use_logprobs:
+        if form.logprobs:
             ops.logprobs_stage2(raw, self.next_tok[sl], LOGPROBS_WIDTH, self.lp_ws, self.lp_tok[sl], self.lp_top_v[sl],
                                 self.lp_top_i[sl], out_count=self.out_count[sl])
 
-    _use_penalties = False
-    _use_logprobs = False
-
-    def _logprob_state(self) -> None:
-        """Allocate the log-probability rings [max_batch, cap(, 20)], the part workspaces and the pinned
-        host twins (first bind that asks)."""
-        if self.lp_tok is not None:
-            return
+    def _ensure_form_state(self, form: SamplingForm) -> None:
+        """Allocate what ``form`` needs and the engine does not hold yet: the penalty history words and
+        parameters; the log-probability rings [max_batch, cap(, 20)], part workspaces and pinned host
+        twins; the raw rows' copy when both are on. Called wherever a form is first known, before any
+        row is bound and before any capture."""
         B, dev, W = self.ecfg.max_batch, self.device, LOGPROBS_WIDTH
-        self.lp_tok = torch.zeros(B, self.cap, dtype=torch.float32, device=dev)
-        self.lp_top_v = torch.zeros(B, self.cap, W, dtype=torch.float32, device=dev)
-        self.lp_top_i = torch.zeros(B, self.cap, W, dtype=torch.int32, device=dev)
-        self.lp_ws = ops.logprobs_workspace(B, W, dev)
-        if self.on_gpu:
-            self.host_lp_tok = torch.zeros(B, self.cap, dtype=torch.float32, pin_memory=True)
-            self.host_lp_top_v = torch.zeros(B, self.cap, W, dtype=torch.float32, pin_memory=True)
-            self.host_lp_top_i = torch.zeros(B, self.cap, W, dtype=torch.int32, pin_memory=True)
+        f32 = dict(dtype=torch.float32, device=dev)
+        if form.penalties and self.pen_words is None:
+            self.pen_words = torch.zeros(B, self.cfg.vocab, dtype=torch.int16, device=dev)
+            self.pen_rep = torch.ones(B, **f32)
+            self.pen_freq = torch.zeros(B, **f32)
+            self.pen_pres = torch.zeros(B, **f32)
+        if form.logprobs and self.lp_tok is None:
+            self.lp_tok = torch.zeros(B, self.cap, **f32)
+            self.lp_top_v = torch.zeros(B, self.cap, W, **f32)
+            self.lp_top_i = torch.zeros(B, self.cap, W, dtype=torch.int32, device=dev)
+            self.lp_ws = ops.logprobs_workspace(B, W, dev)
+            if self.on_gpu:
+                self.host_lp_tok = torch.zeros(B, self.cap, dtype=torch.float32, pin_memory=True)
+                self.host_lp_top_v = torch.zeros(B, self.cap, W, dtype=torch.float32, pin_memory=True)
+                self.host_lp_top_i = torch.zeros(B, self.cap, W, dtype=torch.int32, pin_memory=True)
+        if form.penalties and form.logprobs and self.lp_raw is None:
+            self.lp_raw = torch.zeros(B, self.cfg.vocab, **f32)
 
     def _logprob_entries(self, host: bool, r: int, lo: int, hi: int, n: int) -> list:
         """Columns [lo, hi) of row ``r`` as ``(logprob, [(id, logprob), ...n])`` entries."""
@@ -1050,16 +1031,6 @@ class Engine:
         self.host_lp_top_v[r, lo:hi].copy_(self.lp_top_v[r, lo:hi], non_blocking=True)
         self.host_lp_top_i[r, lo:hi].copy_(self.lp_top_i[r, lo:hi], non_blocking=True)
 
-    def _penalty_state(self) -> None:
-        """Allocate the penalty history words and parameters (first penalised bind)."""
-        if self.pen_words is not None:
-            return
-        B, dev = self.ecfg.max_batch, self.device
-        self.pen_words = torch.zeros(B, self.cfg.vocab, dtype=torch.int16, device=dev)
-        self.pen_rep = torch.ones(B, dtype=torch.float32, device=dev)
-        self.pen_freq = torch.zeros(B, dtype=torch.float32, device=dev)
-        self.pen_pres = torch.zeros(B, dtype=torch.float32, device=dev)
-
     def _bind_sampling(self, r: int, s: "Sequence", p: SamplingParams) -> None:
         """Sampling state of decode row ``r``. A penalised row's history words start from zero with
         the context bit of every id the sequence holds: a sequence bound again (a judge session, an
@@ -1072,16 +1043,13 @@ class Engine:
         if p.logprobs is not None:
             if isinstance(p.logprobs, bool) or not 0 <= int(p.logprobs) <= LOGPROBS_WIDTH:
                 raise EngineError(f"logprobs is an int in [0, {LOGPROBS_WIDTH}], got {p.logprobs!r}")
-            self._logprob_state()
-        if p.penalised:
-            assert len(s.ids) == s.length, (len(s.ids), s.length)
-            self._penalty_state()
         if self.pen_words is None:
             return
         self.pen_rep[r] = p.repetition_penalty
         self.pen_freq[r] = p.frequency_penalty
         self.pen_pres[r] = p.presence_penalty
         if p.penalised:
+            assert len(s.ids) == s.length, (len(s.ids), s.length)
             self.pen_words[r].zero_()
             ids = torch.tensor(s.ids, dtype=torch.int32)
             ops.penalty_seed(self.pen_words[r], ids.to(self.device, non_blocking=True) if self.on_gpu else ids)
@@ -1098,21 +1066,14 @@ class Engine:
         return list(range(len(self.attn_buckets)))
 
     @torch.no_grad()
-    def warmup_graphs(self, batch_sizes: Optional[List[int]] = None, topkp: bool = False,
-                      penalties: bool = False, logprobs: bool = False) -> int:
+    def warmup_graphs(self, batch_sizes: Optional[List[int]] = None, form: SamplingForm = SamplingForm()) -> int:
         """Capture every decode graph this engine can need (per batch size x context bucket) up
         front. A process hosting several engines must do this before serving: a capture running
         beside another engine's work is invalidated by HIP, so serving never captures
-        (``capture_on_demand`` False -> a missing graph runs eagerly). ``topkp`` / ``penalties``:
-        the sampling form the graphs carry (the top-k/top-p launch; the penalty launch ahead of the
-        sampler); ``logprobs``: the two log-probability launches around it; call once per form the
-        process will serve."""
+        (``capture_on_demand`` False -> a missing graph runs eagerly). ``form``: the sampling form the
+        graphs carry; call once per form the process will serve."""
         if not (self.on_gpu and self.ecfg.use_graphs):
             return 0
-        if penalties:
-            self._penalty_state()
-        if logprobs:
-            self._logprob_state()
         self.capture_on_demand = True
         n = 0
         # TP: every rank starts its warm-up steps (eager, with collectives) together — a rank still
@@ -1120,12 +1081,11 @@ class Engine:
         # leaves it with the collectives' protocol state re-synchronised
         self.tp.barrier()
         with self._on_stream():
+            self._ensure_form_state(form)
             for B in batch_sizes or list(range(1, self.ecfg.max_batch + 1)):
                 for bk in self.buckets():
-                    self._use_topkp, self._use_penalties, self._use_logprobs = topkp, penalties, logprobs
-                    self._graph(B, bk)
+                    self._graph(B, bk, form)
                     n += 1
-        self._use_topkp = self._use_penalties = self._use_logprobs = False
         self.capture_on_demand = False
         if self.tp.size > 1:
             self.stream.synchronize()
@@ -1134,43 +1094,40 @@ class Engine:
 
     capture_on_demand = True
 
-    def _graph(self, B: int, bucket: int):
-        key = (B, bool(self._use_topkp), bool(self._use_penalties), bucket)
-        if self._use_logprobs:
-            key += (True,)
+    def _graph(self, B: int, bucket: int, form: SamplingForm):
+        key = GraphKey(B, bucket, form)
         g = self._graphs.get(key)
         if g is not None or not self.capture_on_demand:
             return g
         S = self.ecfg.steps_per_graph
         # warm up once eagerly (kernel attributes, lazy module state) with the device state
         # snapshotted and restored, then capture S steps.
-        snap = self._snapshot_state(B)
-        self._decode_step(B, bucket)
-        self._restore_state(snap, B)
+        snap = self._snapshot_state(B, form)
+        self._decode_step(B, form, bucket)
+        self._restore_state(snap, B, form)
         self.stream.synchronize()
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g, stream=self.stream, capture_error_mode="thread_local"):
             for _ in range(S):
-                self._decode_step(B, bucket)
+                self._decode_step(B, form, bucket)
         self._graphs[key] = g
         return g
 
-    _use_topkp = False
-
-    def _state_tensors(self, B: int):
+    def _state_tensors(self, B: int, form: SamplingForm):
+        """What a decode step in ``form`` writes (the eager warm-up step before a capture is undone)."""
         st = [self.tokens_in, self.positions, self.seq_lens, self.slots, self.out_tokens, self.out_count,
               self.next_tok]
-        if self._use_penalties:  # the eager warm-up step before a capture counts its tokens there
+        if form.penalties:  # the step counts its tokens there
             st.append(self.pen_words[:B])
-        if self._use_logprobs:  # ... and writes a column of the rings
+        if form.logprobs:  # ... and writes a column of the rings
             st += [self.lp_tok[:B], self.lp_top_v[:B], self.lp_top_i[:B]]
         return st
 
-    def _snapshot_state(self, B: int):
-        return [t.clone() for t in self._state_tensors(B)]
+    def _snapshot_state(self, B: int, form: SamplingForm):
+        return [t.clone() for t in self._state_tensors(B, form)]
 
-    def _restore_state(self, snap, B: int) -> None:
-        for dst, src in zip(self._state_tensors(B), snap):
+    def _restore_state(self, snap, B: int, form: SamplingForm) -> None:
+        for dst, src in zip(self._state_tensors(B, form), snap):
             dst.copy_(src)
 
     @torch.no_grad()
@@ -1190,9 +1147,8 @@ class Engine:
         eos_set = set(self.cfg.eos)
         with self._on_stream(), trace.span("decode", engine=self.name, rows=B):
             max_new = max(p.max_tokens for p in params)
-            self._use_topkp = any(p.topkp for p in params)
-            self._use_penalties = any(p.penalised for p in params)
-            self._use_logprobs = any(p.logprobs is not None for p in params)
+            form = SamplingForm.of(params)
+            self._ensure_form_state(form)
             for i, (s, p) in enumerate(zip(seqs, params)):
                 if not s.has_logits:
                     raise EngineError("sequence has no prefill logits")
@@ -1201,7 +1157,7 @@ class Engine:
             if max_new > self.cap - S - 1:
                 raise EngineError("max_tokens exceeds engine capacity")
             # first token from the prefill logits (+ device state advance)
-            self._sample(B, self._gather_logits(B))
+            self._sample(B, self._gather_logits(B), form)
             produced = [0] * B
             done = [False] * B
             results = Tokens([] for _ in range(B))
@@ -1272,7 +1228,7 @@ class Engine:
                         failure = e
                     if agree():
                         break
-                    self._decode_step(B)
+                    self._decode_step(B, form)
                     issued += 1
                 self._check_collectives()
                 self._finish(seqs, results)
@@ -1313,12 +1269,12 @@ class Engine:
                         self._inject("decode", issued)
                         # context reached by the end of this replay decides the attention bucket
                         bucket = self._bucket(base_len + issued + S + 1)
-                        graph = self._graph(B, bucket) if self.ecfg.use_graphs else None
+                        graph = self._graph(B, bucket, form) if self.ecfg.use_graphs else None
                         if graph is not None:
                             graph.replay()
                         else:
                             for _ in range(S):
-                                self._decode_step(B, bucket)
+                                self._decode_step(B, form, bucket)
                         issued += S
                     # wait for the previous snapshot (the GPU keeps the just-issued replay queued)
                     self._wait_event(pending_ev)
@@ -1469,15 +1425,39 @@ class Engine:
                               "request's tokens are invalid")
 
     def _bind_rows(self, seqs: List[Sequence], params: List[SamplingParams]) -> None:
-        """Bind sequences to decode rows 0..B-1: block tables, prefill logits and sampling state."""
-        B = len(seqs)
-        self.block_tables[:B].copy_(self._block_table(seqs))
+        """Bind sequences to decode rows 0..B-1: block tables (one batched copy), then each row."""
+        self.block_tables[:len(seqs)].copy_(self._block_table(seqs))
         for i, (s, p) in enumerate(zip(seqs, params)):
             s.row = i
-            self.logits_local[i].copy_(s.logits)
-            self._bind_sampling(i, s, p)
-            self.positions[i] = s.length - 1
-            self.out_count[i] = 0
+            self._bind_row(i, s, p)
+
+    def _bind_row(self, r: int, s: Sequence, p: SamplingParams) -> None:
+        """The per-row part of a bind (``_bind_rows``, the batcher's ``admit``): prefill logits, sampling
+        state, position, no token produced yet. ``_ensure_form_state(p.form)`` came first."""
+        self.logits_local[r].copy_(s.logits)
+        self._bind_sampling(r, s, p)
+        self.positions[r] = s.length - 1
+        self.out_count[r] = 0
+
+    def row_state(self) -> List[torch.Tensor]:
+        """Every tensor whose row r belongs to decode row r across steps: the only list of per-row
+        sampling state (the log-probability rings move by columns, see ``move_row``)."""
+        st = [self.tokens_in, self.positions, self.seq_lens, self.slots, self.block_tables, self.out_tokens,
+              self.out_count, self.next_tok, self.inv_temp, self.top_k, self.top_p, self.seeds, self.ln_min_p]
+        if self.pen_words is not None:
+            st += [self.pen_words, self.pen_rep, self.pen_freq, self.pen_pres]
+        return st
+
+    def move_row(self, dst: int, src: int, lp_cols: Optional[tuple] = None) -> None:
+        """Decode row ``src`` becomes row ``dst`` (device copies on the engine stream); ``lp_cols`` =
+        (lo, hi): its columns [lo, hi) of the log-probability rings travel with it."""
+        with self._on_stream():
+            for buf in self.row_state():
+                buf[dst].copy_(buf[src])
+            if lp_cols is not None:
+                lo, hi = lp_cols
+                for buf in (self.lp_tok, self.lp_top_v, self.lp_top_i):
+                    buf[dst, lo:hi].copy_(buf[src, lo:hi])
 
     @torch.no_grad()
     def debug_decode_logits(self, prompt: Seq[int], n: int):
@@ -1506,16 +1486,15 @@ class Engine:
                 for s in seqs:
                     self._reserve(s, s.length + n + 2)
                 params = params or [SamplingParams(n, 0.0, 1.0, 0, 0, False)] * B
-                self._use_topkp = any(p.topkp for p in params)
-                self._use_penalties = any(p.penalised for p in params)
-                self._use_logprobs = any(p.logprobs is not None for p in params)
+                form = SamplingForm.of(params)
+                self._ensure_form_state(form)
                 self._bind_rows(seqs, params)
                 rows = self._debug_raw_logits = [self.logits_local[:B].clone()]
                 try:
-                    self._sample(B, self._gather_logits(B))
+                    self._sample(B, self._gather_logits(B), form)
                     bucket = self._bucket(max(s.length for s in seqs) + n + 2)
                     for _ in range(n - 1):
-                        self._decode_step(B, bucket)
+                        self._decode_step(B, form, bucket)
                 finally:
                     self._debug_raw_logits = None
                 toks = self.out_tokens[:B, :n].clone()

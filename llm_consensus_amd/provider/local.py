@@ -32,6 +32,7 @@ from ..context import Context, ContextError
 from ..parallel.placement import (HBM_BYTES, USABLE_FRACTION, ModelDemand, alone_plan, default_gpus, describe,
                                   packed_weights_mode,
                                   fused_ar_plan, solve)
+from ..sampling import SamplingParams
 from ..utils import trace as tracing
 from ..utils.tokenizer import tokenizer_for
 from .base import Request, Response, StreamCallback
@@ -105,9 +106,8 @@ def sampling_knobs(req: Optional[Request], config, model_sampling: bool) -> dict
 
 def sampling_form(req: Optional[Request], config, model_sampling: bool) -> tuple:
     """(top-k/top-p launch, penalty launch) the decode graphs of such requests carry."""
-    k = sampling_knobs(req, config, model_sampling)
-    return (k["top_k"] > 0 or k["top_p"] < 1.0 or k["min_p"] > 0.0,
-            k["repetition_penalty"] != 1.0 or k["presence_penalty"] != 0.0 or k["frequency_penalty"] != 0.0)
+    p = SamplingParams(**sampling_knobs(req, config, model_sampling))
+    return (p.topkp, p.penalised)
 
 
 def _free_port() -> int:

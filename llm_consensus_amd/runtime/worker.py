@@ -415,7 +415,7 @@ def worker_main(gpu: int, conn, models: List[dict], dist_info: Optional[dict], t
 
             from ..context import Context
             from .. import ops
-            from ..engine import Engine, EngineConfig
+            from ..engine import Engine, EngineConfig, SamplingForm
             from ..models.config import FAMILIES
             from ..parallel.comm import TPGroup
 
@@ -482,11 +482,11 @@ def worker_main(gpu: int, conn, models: List[dict], dist_info: Optional[dict], t
                     h.engine.warmup_graphs()
                     # ... and those of the run's sampling form when it is not the default one, so a
                     # top-k or penalised run does not decode eagerly in a process of several engines
-                    topkp, pen = forms.get(h.name, (False, False))
-                    if topkp or pen:
-                        h.engine.warmup_graphs(topkp=topkp, penalties=pen)
+                    form = SamplingForm(*forms.get(h.name, (False, False)))
+                    if form != SamplingForm():
+                        h.engine.warmup_graphs(form=form)
                     if want_lp.get(h.name):
-                        h.engine.warmup_graphs(topkp=topkp, penalties=pen, logprobs=True)
+                        h.engine.warmup_graphs(form=form._replace(logprobs=True))
             torch.cuda.synchronize()
         send(("ready", {"gpu": gpu, "models": list(hosts)}))
     except Exception as e:  # noqa: BLE001

@@ -20,7 +20,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
 from llm_consensus_amd import ops  # noqa: E402
-from llm_consensus_amd.engine import Engine, EngineConfig  # noqa: E402
+from llm_consensus_amd.engine import Engine, EngineConfig, SamplingForm  # noqa: E402
 from llm_consensus_amd.models.config import FAMILIES  # noqa: E402
 
 ap = argparse.ArgumentParser()
@@ -49,7 +49,7 @@ e = Engine(cfg, EngineConfig(device="cuda:0", max_context=a.ctx, seed=1))
 # every bucket's decode graph of the four forms now: nothing is captured inside a timed run
 for pen in (False, True):
     for lp in (False, True):
-        e.warmup_graphs([1], penalties=pen, logprobs=lp)
+        e.warmup_graphs([1], SamplingForm(penalties=pen, logprobs=lp))
 outs = {tag: e.generate_ids(prompt, 16, temperature=0.0, stop_on_eos=False, **kw) for tag, kw in forms.items()}
 assert list(outs["off"]) == list(outs["logprobs20"]) and list(outs["penalised"]) == list(outs["penalised_logprobs20"])
 emit("engine", {"packed": bool(e.packed), "graphs": sorted(str(k) for k in e._graphs), "vocab": cfg.vocab})

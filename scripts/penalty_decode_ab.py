@@ -21,7 +21,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
 from llm_consensus_amd import ops  # noqa: E402
-from llm_consensus_amd.engine import Engine, EngineConfig  # noqa: E402
+from llm_consensus_amd.engine import Engine, EngineConfig, SamplingForm  # noqa: E402
 from llm_consensus_amd.models.config import FAMILIES  # noqa: E402
 
 ap = argparse.ArgumentParser()
@@ -48,7 +48,7 @@ PEN = dict(repetition_penalty=1.3, frequency_penalty=0.2, presence_penalty=0.5)
 forms = {"plain": {}, "penalised": PEN}
 e = Engine(cfg, EngineConfig(device="cuda:0", max_context=a.ctx, seed=1))
 e.warmup_graphs([1])  # every bucket's decode graph of both forms now: nothing is captured inside a timed run
-e.warmup_graphs([1], penalties=True)
+e.warmup_graphs([1], SamplingForm(penalties=True))
 for kw in forms.values():
     e.generate_ids(prompt, 16, temperature=0.0, stop_on_eos=False, **kw)
 emit("engine", {"packed": bool(e.packed), "graphs": sorted(str(k) for k in e._graphs), "vocab": cfg.vocab})

@@ -183,7 +183,7 @@ def test_attention_fault_in_flight_replay_is_not_lost(cuda):
             if inject["on"]:
                 eng.attn_fault.fill_(1)  # on the engine stream, after the replay's kernels
 
-    eng._graph = lambda B, bk: Faulting(real_graph(B, bk))
+    eng._graph = lambda B, bk, form: Faulting(real_graph(B, bk, form))
     sa, sb = eng.new_sequence(), eng.new_sequence()
     eng.prefill([sa], [[100 + i for i in range(20)]])
     eng.prefill([sb], [[200 + i for i in range(20)]])

@@ -176,7 +176,7 @@ def test_engine_graph_decode_equals_eager_steps(cuda, pen):
     e = ee.generate_ids(PROMPT, 24, **kw)
     assert len(g) == 24 == len(g.logprobs) and all(len(top) == 20 for _, top in g.logprobs)
     assert list(g) == list(e) and _bits(g.logprobs) == _bits(e.logprobs)
-    assert any(len(k) == 5 and k[4] and k[2] == bool(pen) for k in eg._graphs) and not ee._graphs
+    assert any(k.form.logprobs and k.form.penalties == bool(pen) for k in eg._graphs) and not ee._graphs
     assert [t for _, top in g.logprobs for t, _ in top[:1]] != list(g)  # sampled, not always the argmax
 
 
@@ -189,7 +189,7 @@ def test_engine_tokens_do_not_depend_on_logprobs(cuda, kw):
     each row truncated to the n it asked for; the off run holds no ring and no new graph key."""
     eg, _ = _engines()
     off = eg.generate_ids(PROMPT, 20, stop_on_eos=False, **kw)
-    assert off.logprobs is None and eg.lp_tok is None and all(len(k) == 4 for k in eg._graphs)
+    assert off.logprobs is None and eg.lp_tok is None and not any(k.form.logprobs for k in eg._graphs)
     for n in (0, 3):
         on = eg.generate_ids(PROMPT, 20, stop_on_eos=False, logprobs=n, **kw)
         assert list(on) == list(off) and len(on.logprobs) == 20
@@ -286,7 +286,7 @@ def _tp_worker(rank, world, port, q):
     try:
         torch.cuda.set_device(0)
         dist.init_process_group("gloo", init_method=f"tcp://127.0.0.1:{port}", rank=rank, world_size=world)
-        from llm_consensus_amd.engine import Engine, EngineConfig
+        from llm_consensus_amd.engine import Engine, EngineConfig, SamplingForm
         from llm_consensus_amd.models.config import FAMILIES
         from llm_consensus_amd.parallel.comm import TPGroup
 
@@ -294,13 +294,13 @@ def _tp_worker(rank, world, port, q):
         tp.enable_custom("cuda:0")
         e = Engine(FAMILIES["llama-small"], EngineConfig(device="cuda:0", max_context=512, seed=5), tp=tp)
         e.warmup_graphs([1])
-        e.warmup_graphs([1], logprobs=True)
+        e.warmup_graphs([1], SamplingForm(logprobs=True))
         kw = dict(temperature=1.0, seed=9, top_k=0, stop_on_eos=False)
         off = e.generate_ids(PROMPT, 24, **kw)
         on = e.generate_ids(PROMPT, 24, logprobs=5, **kw)
         torch.cuda.synchronize()
         ring = [t[0, :24].cpu().numpy().tobytes() for t in (e.lp_tok, e.lp_top_v, e.lp_top_i)]
-        graphs = sorted(k for k in e._graphs if len(k) == 5)
+        graphs = sorted((k.rows, tuple(k.form)) for k in e._graphs if k.form.logprobs)  # plain values
         q.put((rank, (list(off), list(on), ring, on.logprobs, graphs), tp.custom_timed_out()))
         dist.barrier()
         dist.destroy_process_group()
@@ -331,7 +331,7 @@ def test_tp2_logprobs(cuda):
         assert not got[r][1]
         off, on, ring, entries, graphs = got[r][0]
         assert off == on and len(on) == 24
-        assert graphs and all(k[0] == 1 and k[4] for k in graphs)  # the form was captured, not run eagerly
+        assert graphs and all(rows == 1 and form[2] for rows, form in graphs)  # the form was captured, not run eagerly
     assert got[0][0][1] == got[1][0][1] and got[0][0][2] == got[1][0][2]
     lead, peer = got[0][0][3], got[1][0][3]
     assert len(lead) == 24 and all(len(top) == 5 for _, top in lead) and peer == []

@@ -393,6 +393,31 @@ def test_model_sampling_precedence(tmp_path):
     assert p.penalised and p.topkp and p.repetition_penalty == 1.2
 
 
+def test_sampling_form_is_the_params_own_predicates(tmp_path):
+    """The provider's (top-k/top-p launch, penalty launch) pair restates nothing: over the request and
+    config cases above it is what SamplingParams says of the same knobs."""
+    from llm_consensus_amd.engine.engine import SamplingParams
+    from llm_consensus_amd.models.checkpoint import config_from_hf
+    from llm_consensus_amd.models.config import FAMILIES
+    from llm_consensus_amd.provider.base import Request
+    from llm_consensus_amd.provider.local import sampling_form, sampling_knobs
+
+    cfg = config_from_hf(_tiny_checkpoint(tmp_path, {"repetition_penalty": 1.05, "temperature": 0.7, "top_k": 20,
+                                                     "top_p": 0.8, "min_p": 0.01}))
+    bare = Request(model="m", prompt="p")
+    req = Request(model="m", prompt="p", temperature=1.0, top_k=0, top_p=0.95, repetition_penalty=1.2,
+                  presence_penalty=0.5)
+    cases = [(bare, cfg, False), (bare, cfg, True), (req, cfg, True), (req, cfg, False),
+             (bare, FAMILIES["llama-tiny"], True), (Request(model="m", prompt="p", min_p=0.1), FAMILIES["llama-tiny"], False),
+             (None, None, False)]
+    seen = set()
+    for r, c, ms in cases:
+        p = SamplingParams(**sampling_knobs(r, c, ms))
+        assert sampling_form(r, c, ms) == (p.topkp, p.penalised) == tuple(p.form[:2])
+        seen.add(sampling_form(r, c, ms))
+    assert seen == {(False, False), (True, False), (True, True)}
+
+
 # -- engine -------------------------------------------------------------------------------------------
 def _tiny_engine(**kw):
     from llm_consensus_amd.engine.engine import Engine, EngineConfig

@@ -177,7 +177,7 @@ def test_engine_graph_decode_equals_eager_steps(cuda):
     eg, ee = _engines()
     sp = SamplingParams(24, 1.0, 1.0, 40, 11, False, **PEN)
     graph = eg.generate_ids(PROMPT, 24, temperature=1.0, top_k=40, seed=11, stop_on_eos=False, **PEN)
-    assert any(k[2] for k in eg._graphs) and len(graph) == 24
+    assert any(k.form.penalties for k in eg._graphs) and len(graph) == 24
     toks, lg = ee.debug_decode_logits_batch([PROMPT], 24, params=[sp])
     assert graph == toks[0]
     pr.check_steps(toks[0], lg[0].numpy(), PROMPT, sp)
@@ -245,7 +245,7 @@ def _tp_worker(rank, world, port, q):
     try:
         torch.cuda.set_device(0)
         dist.init_process_group("gloo", init_method=f"tcp://127.0.0.1:{port}", rank=rank, world_size=world)
-        from llm_consensus_amd.engine import Engine, EngineConfig
+        from llm_consensus_amd.engine import Engine, EngineConfig, SamplingForm
         from llm_consensus_amd.models.config import FAMILIES
         from llm_consensus_amd.parallel.comm import TPGroup
 
@@ -253,10 +253,10 @@ def _tp_worker(rank, world, port, q):
         tp.enable_custom("cuda:0")
         e = Engine(FAMILIES["llama-small"], EngineConfig(device="cuda:0", max_context=512, seed=5), tp=tp)
         e.warmup_graphs()
-        e.warmup_graphs(penalties=True)
+        e.warmup_graphs(form=SamplingForm(penalties=True))
         gen = e.generate_ids(PROMPT, 32, temperature=0.0, stop_on_eos=False, presence_penalty=1e4)
         torch.cuda.synchronize()
-        graphs = sorted(k[:3] for k in e._graphs)
+        graphs = sorted((k.rows, tuple(k.form)) for k in e._graphs)  # (rows, (topkp, penalties, logprobs))
         q.put((rank, gen, graphs, tp.custom_timed_out()))
         dist.barrier()
         dist.destroy_process_group()
@@ -285,6 +285,6 @@ def test_tp2_penalised_decode(cuda):
     for r in (0, 1):
         assert not isinstance(got[r][0], str), got[r][0]
         assert not got[r][2]
-        assert (1, False, True) in got[r][1]  # the penalised form was captured, not run eagerly
+        assert (1, (False, True, False)) in got[r][1]  # the penalised form was captured, not run eagerly
     assert got[0][0] == got[1][0]
     assert len(got[0][0]) == 32 == len(set(got[0][0]))

@@ -114,6 +114,7 @@ def test_driver_process_stays_torch_free():
 
     code = ("import sys, llm_consensus_amd.cli, llm_consensus_amd.provider.local, "
             "llm_consensus_amd.runtime.worker, llm_consensus_amd.server, llm_consensus_amd.parallel.placement; "
+            "llm_consensus_amd.provider.local.sampling_form(None, None, False); "
             "print('torch' in sys.modules)")
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stderr

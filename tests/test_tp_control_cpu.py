@@ -61,9 +61,9 @@ def _cancel_worker(rank, world, port, cancel_at, q):
         steps = [0]
         orig = e._decode_step
 
-        def counted(B, bucket=None):
+        def counted(*args):
             steps[0] += 1
-            return orig(B, bucket)
+            return orig(*args)
 
         e._decode_step = counted
         p = [(i * 13) % 700 + 256 for i in range(16)]
